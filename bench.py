@@ -13,8 +13,15 @@ one MI355X: the 1.6M x 2048 fp32 gallery is 13.1 GB of the 288 GB HBM):
   work is fixed as N grows ("weak" scaling): value = N * B * K / max-over-ranks time.
 
 One JSON line on rank 0 with the contract keys plus `roofline` (dominant
-kernel by measured time, HIP events on the launch stream), `roofline_by_kernel`
-and `cpu_baseline` (oracle CPU restatement of the reference path, rank 0, N=1).
+kernel by measured time, HIP events on the launch stream of the timed steps)
+and `roofline_by_kernel`.
+
+A plain run sets up, warms up, times --steps steps, writes the last timed
+step's outputs if --dump-outputs DIR is given, and prints the line.  --full
+adds everything that takes work of its own: the prefilter == exhaustive and
+row-as-query checks before the timed loop, the exhaustive-ranker leg, the
+other schedule, the decorrelated-query sweep, C2's synchronised phase step and
+`cpu_baseline` (oracle CPU restatement of the reference path, rank 0, N=1).
 """
 import argparse
 import json
@@ -376,10 +383,12 @@ def run_c2(a, world, rank, dev):
 
     for _ in range(a.warmup):
         step()
-    marks = []
-    step(marks)  # one more untimed step with a sync at every phase boundary
-    phases = {b[0]: round((b[1] - a_[1]) * 1e3, 2) for a_, b in zip(marks, marks[1:])}
-    log(f"[rank {rank}] c2 phases (ms, synchronised step): {phases}")
+    phases = None
+    if a.full:
+        marks = []
+        step(marks)  # one more untimed step with a sync at every phase boundary
+        phases = {b[0]: round((b[1] - a_[1]) * 1e3, 2) for a_, b in zip(marks, marks[1:])}
+        log(f"[rank {rank}] c2 phases (ms, synchronised step): {phases}")
     acct["on"] = True
     if DIST_ON:
         dist.barrier()
@@ -395,6 +404,8 @@ def run_c2(a, world, rank, dev):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs and rank == 0 and maps:  # the last timed step's result: (easy, medium, hard) mAP per set
+        dump_outputs(a.dump_outputs, {"map_" + k: np.asarray(v, dtype=np.float64) for k, v in maps.items()})
     units = sum(st["n_g"] + st["n_q"] for st in sets)
     value = units * a.steps / elapsed
     # algorithmic FLOPs of this rank's share: every image's trunk convs + the 2048->512 projection
@@ -438,7 +449,7 @@ def run_c2(a, world, rank, dev):
            "map_easy_medium_hard": {k: list(v) for k, v in maps.items()} if maps else None,
            "phases_ms_synchronised_step": phases,
            "roofline": roof, "roofline_by_kernel": rk}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         t = time.time()
         res["cpu_baseline"] = cpu_baseline_c2([(st["n_g"], st["n_q"]) for st in sets])
         log(f"cpu baseline {time.time() - t:.1f}s")
@@ -471,6 +482,31 @@ def _json_scalar(o):
     if hasattr(o, "item"):
         return o.item()
     raise TypeError(f"not JSON serializable: {type(o).__name__}")
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """--dump-outputs: what the last timed step returned, as DIR/<name>.npy
+    (rank r of an N > 1 run: DIR/<name>_rank<r>.npy).  Floating arrays are
+    written as float32 (float64 stays float64), integer arrays as float64
+    (exact below 2^53).  At most DUMP_MAX_BYTES over all ranks and arrays: an
+    array above its share is cut to a fixed, seeded sample of its rows."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, world * len(arrays))
+    for name, arr in arrays.items():
+        if isinstance(arr, torch.Tensor):
+            arr = arr.detach().cpu()
+            arr = (arr.float() if arr.is_floating_point() and arr.dtype != torch.float64 else arr.double()).numpy()
+        else:
+            arr = np.asarray(arr)
+            arr = arr.astype(np.float32 if arr.dtype.kind == "f" and arr.dtype.itemsize < 8 else np.float64)
+        arr = np.atleast_1d(arr)
+        if arr.nbytes > share:
+            keep = max(1, share // max(1, arr.nbytes // arr.shape[0]))
+            arr = arr[np.sort(np.random.RandomState(0).choice(arr.shape[0], keep, replace=False))]
+        np.save(os.path.join(dirname, name + ("" if world == 1 else f"_rank{rank}") + ".npy"), arr)
 
 
 def main():
@@ -513,10 +549,17 @@ def main():
                     help="C3: the trunk's batch cut into this many parts, each on its own HIP stream, part i+1 one "
                          "conv behind part i (networks forward_test_u8_streams; bit-identical to serial parts); "
                          "default 1; C3 also reports the overlapped schedule (2 streams + pipelined ranker)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the prefilter == exhaustive and "
+                         "row-as-query checks, the exhaustive-ranker leg, the other schedule, the decorrelated-query "
+                         "sweep, C2's synchronised phase step and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(scores and indices; C2: each set's mAP triple), float32 / float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the side measurements after the timed loop (the decorrelated-query sweep and the "
-                         "overlapped schedule): tools/profile.sh, so that the profile holds the timed loop's launches")
+                    help="with --full: skip the side measurements after the timed loop (the decorrelated-query "
+                         "sweep and the overlapped schedule)")
     ap.add_argument("--c2-dataset", choices=("both", "roxford5k", "rparis6k"), default="both",
                     help="C2 sets per step (BASELINE C2: full ROxford5k + RParis6k)")
     ap.add_argument("--c2-gallery", type=int, default=0, help="override every C2 set's gallery size (0: revisitop's)")
@@ -686,7 +729,7 @@ def main():
     out = run_steps(a.warmup) if a.warmup > 0 else None
     torch.cuda.synchronize()
     prefilter_stats = None
-    if gal_bf is not None:  # the prefilter must reproduce the exhaustive fp32 ranking bit for bit
+    if gal_bf is not None and a.full:  # the prefilter must reproduce the exhaustive fp32 ranking bit for bit
         d0 = embed()
         s_p, i_p = ops.cosine_topk_prefilter(d0, gallery, gal_bf, gal_bound, a.k, idx_offset=lo, workspace=ws,
                                              max_workspace_bytes=ws_max)
@@ -702,12 +745,12 @@ def main():
         prefilter_stats = {"bf16_filter_survivors_per_query": {"mean": round(surv.mean().item(), 1),
                                                                "min": int(surv.min().item()),
                                                                "max": int(surv.max().item())}}
-    # sanity: a gallery row used as a query must come back first
-    chk_s, chk_i = ops.cosine_topk(gallery[:2].contiguous(), gallery, 1, idx_offset=lo, workspace=ws)
-    assert chk_i[:, 0].tolist() == [lo, lo + 1], chk_i
-    if sharded is not None:  # the full sharded path: all-gather -> shard top-k -> all-to-all -> merge
-        ss, si = sharded.search(gallery[:2].contiguous(), a.k, [2] * world)
-        assert si[:, 0].tolist() == [lo, lo + 1], si[:, :3]
+    if a.full:  # sanity: a gallery row used as a query must come back first
+        chk_s, chk_i = ops.cosine_topk(gallery[:2].contiguous(), gallery, 1, idx_offset=lo, workspace=ws)
+        assert chk_i[:, 0].tolist() == [lo, lo + 1], chk_i
+        if sharded is not None:  # the full sharded path: all-gather -> shard top-k -> all-to-all -> merge
+            ss, si = sharded.search(gallery[:2].contiguous(), a.k, [2] * world)
+            assert si[:, 0].tolist() == [lo, lo + 1], si[:, :3]
 
     timer = ops.KernelTimer(dev.index)
     timer.enable(True)
@@ -731,9 +774,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     value = world * a.batch * a.steps / elapsed
+    if a.dump_outputs and out is not None:  # the last timed step's (scores, indices), before anything reuses ws
+        dump_outputs(a.dump_outputs, {"scores": out[0], "indices": out[1]}, rank, world)
 
     exhaustive = None
-    if gal_bf is not None:  # the same step with the exhaustive fp32 ranker, for comparison
+    if gal_bf is not None and a.full:  # the same step with the exhaustive fp32 ranker, for comparison
         timer.enable(True)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -756,7 +801,7 @@ def main():
                       "bit_identical_to_prefilter": True}
 
     alt_sched, alt_cls = None, None
-    if c3 and not DIST_ON and not a.no_extras:
+    if c3 and not DIST_ON and a.full and not a.no_extras:
         # the other schedule: one stream if the timed loop overlapped, else the
         # overlapped one; same steps, after one untimed step
         main_sched = dict(sched)
@@ -786,7 +831,7 @@ def main():
         sched.update(main_sched)
 
     decorrelated = None
-    if gal_bf is not None and not a.no_extras:
+    if gal_bf is not None and a.full and not a.no_extras:
         # The seeded random-weight trunk maps every image to nearly the same
         # descriptor (pairwise cosine ~1.0), so the timed queries are one
         # direction repeated.  The same ranker on q_total independent Gaussian
@@ -975,7 +1020,7 @@ def main():
                          **({"decorrelated_queries": decorrelated} if decorrelated else {})}
     if alt_sched is not None:
         res["one_stream_schedule" if alt_sched["embed_streams"] == 1 else "overlapped_schedule"] = alt_sched
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.workload == "c3":
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline and a.workload == "c3":
         t = time.time()
         res["cpu_baseline"] = cpu_baseline(a.arch, a.gallery, a.dim, a.k)
         log(f"cpu baseline {time.time() - t:.1f}s")

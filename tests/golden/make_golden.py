@@ -53,6 +53,9 @@ def loader_fixture():
                 ds = ImageFromList(paths, imsize=imsize, bbox=I.LOADER_BBOXES if use_bb else None)
                 for i in range(len(ds)):
                     out[f"im{imsize}_b{use_bb}_{i}"] = np.asarray(ds[i])
+    # two files, each below 1 MiB: the full-size outputs, and the seed with the thumbnails
+    full = {k: out.pop(k) for k in list(out) if k.startswith("imNone_")}
+    np.savez_compressed(os.path.join(HERE, "loader_full.npz"), **full)
     np.savez_compressed(os.path.join(HERE, "loader.npz"), seed=61, **out)
 
 

@@ -1,5 +1,5 @@
 """Host-side loader (dataset.py) against the reference's ImageFromList outputs
-(tests/golden/loader.npz, made by make_golden.py from dataset/ImageFromList.py
+(tests/golden/loader.npz and loader_full.npz, made by make_golden.py from dataset/ImageFromList.py
 with Image.ANTIALIAS restored as LANCZOS), the gnd reader and the revisitop
 config restatement."""
 import os
@@ -19,7 +19,8 @@ import inputs as I  # noqa: E402
 @pytest.mark.parametrize("imsize", [None, 100, 57])
 @pytest.mark.parametrize("use_bb", [0, 1])
 def test_image_from_list_matches_reference(tmp_path, imsize, use_bb):
-    fx = np.load(os.path.join(GOLD, "loader.npz"))
+    # the full-size outputs live in a file of their own (each fixture stays below 1 MiB)
+    fx = {**np.load(os.path.join(GOLD, "loader.npz")), **np.load(os.path.join(GOLD, "loader_full.npz"))}
     paths = I.write_pngs(I.loader_images(int(fx["seed"])), str(tmp_path))
     ds = D.ImageFromList(paths, imsize=imsize, bbox=I.LOADER_BBOXES if use_bb else None)
     for i in range(len(ds)):

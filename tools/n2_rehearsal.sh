@@ -5,7 +5,7 @@ set -o pipefail
 O=gpurun_out/n2
 mkdir -p $O
 export RR_DIST_BACKEND=gloo
-timeout -k 10 400 python -u bench.py --gpus 2 --steps 3 --warmup 1 > $O/c3.json 2> $O/c3.err && \
-timeout -k 10 400 python -u bench.py --gpus 2 --steps 3 --warmup 1 --workload c5 > $O/c5.json 2> $O/c5.err && \
-timeout -k 10 400 python -u bench.py --gpus 2 --steps 3 --warmup 1 --workload c4 > $O/c4.json 2> $O/c4.err && \
+timeout -k 10 400 python -u bench.py --full --gpus 2 --steps 3 --warmup 1 > $O/c3.json 2> $O/c3.err && \
+timeout -k 10 400 python -u bench.py --full --gpus 2 --steps 3 --warmup 1 --workload c5 > $O/c5.json 2> $O/c5.err && \
+timeout -k 10 400 python -u bench.py --full --gpus 2 --steps 3 --warmup 1 --workload c4 > $O/c4.json 2> $O/c4.err && \
 echo all-done
