@@ -64,10 +64,11 @@ typedef struct rr_handle_s* rr_handle_t;
  * than the two launches it fused) and the split-bf16 core's rr_conv2d_s3 /
  * rr_linear_s3 / rr_split3_bf16 (superseded by the f16x2 core in round 3);
  * the tuning keys RR_TUNE_SWEEP_FORM (14) and RR_TUNE_HALO_2D (15) were
- * added (round 6).
+ * added (round 6); 7 = entries ADDED: rr_dolg_local_pool and
+ * rr_dolg_orth_fuse (the DOLG head; no existing entry changed).
  * Bindings compare rr_abi_version() with the RR_ABI_VERSION they were
  * written against.                                                          */
-#define RR_ABI_VERSION 6
+#define RR_ABI_VERSION 7
 int rr_abi_version(void);
 
 /* ---- handle ------------------------------------------------------------ */
@@ -542,6 +543,34 @@ int rr_attention_bf16_qkv16(rr_handle_t h, const void* qkv_bf16, int b, int seq,
  * utils/helpfunc.py:44, iris_evaluate.py:379-380).                        */
 int rr_l2_normalize(rr_handle_t h, const float* x, int m, int d, float eps,
                     float* y, void* stream);
+
+/* ---- DOLG head (networks/RetrievalNet.py:409-474, with_aspp=False) ------ */
+/* The local branch's attention-weighted pooling in ONE read of the map.
+ * y [b][hw][c] fp32 NHWC = bn(conv1(f3)) (pre-ReLU), w2 [c] and b2 = conv2's
+ * weight and bias; out [b][c] =
+ *   m = mean_p softplus(w2 . relu(y_p) + b2) * y_p / max(||y_p||_2, 1e-12)
+ * (softplus: x for x > 20, else log1p(exp(x)); an all-zero pixel adds exactly
+ * 0).  Replaces SpatialAttention2d.forward after the BN (:466-473: F.normalize
+ * over channels, ReLU, conv2, softplus, expand, multiply) and, together with
+ * rr_dolg_orth_fuse, DOLG.forward_test's two bmm, the division, the
+ * subtraction and pool_l (:420-426): the projection is linear in the local
+ * map, so only its mean m is needed and neither map is ever written.
+ * c % 256 == 0, c <= 2048, hw > 0, y / w2 / out 16-B aligned (else RR_EINVAL);
+ * b == 0 is RR_OK with no launch.  No float atomics: where few images leave
+ * the chip short of work, an image's pixels are split over workgroups whose
+ * partial sums go to a buffer the handle keeps per stream (allocated on first
+ * use) and are added in a fixed order; the split depends on (b, hw) alone, so
+ * the result is the same bits on every run.                                 */
+int rr_dolg_local_pool(rr_handle_t h, const float* y, int b, int hw, int c,
+                       const float* w2, float b2, float* out, void* stream);
+
+/* Orthogonal fusion: out [b][2c] = [fg | m - fg (fg . m) / (fg . fg)] for fg,
+ * m [b][c].  Replaces DOLG.forward_test's torch.norm / bmm / bmm / divide /
+ * subtract / pool_l / torch.cat (:418-428) given m from rr_dolg_local_pool.
+ * No epsilon on fg . fg: a zero fg row gives NaN, as the reference's division
+ * does.  c % 4 == 0, 16-B aligned rows.                                     */
+int rr_dolg_orth_fuse(rr_handle_t h, const float* fg, const float* m, int b,
+                      int c, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("RR_LIB_PATH") or os.path.join(_HERE, "librr.so")
 CSRC = os.path.join(_HERE, "csrc")
 
 RR_OK, RR_EINVAL, RR_EHIP, RR_EWORKSPACE, RR_EOVERFLOW = 0, -1, -2, -3, -4
-ABI_VERSION = 6  # RR_ABI_VERSION of include/rr.h these signatures follow
+ABI_VERSION = 7  # RR_ABI_VERSION of include/rr.h these signatures follow
 AMAX_SLOTS = 64  # RR_AMAX_SLOTS
 
 # timing classes (rr_timing_enable / rr_timing_collect)
@@ -71,6 +71,8 @@ SIGNATURES = {
     "rr_gem_pool": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp]),
     "rr_linear": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "rr_l2_normalize": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp]),
+    "rr_dolg_local_pool": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _vp, _vp]),
+    "rr_dolg_orth_fuse": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "rr_linear_ex": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp]),
     "rr_layernorm": (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp, _f, _vp, _vp]),
     "rr_patchify": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -100,6 +100,7 @@ int rr_destroy(rr_handle_t h) {
       (void)hipEventDestroy(h->ev_start[c][i]);
       (void)hipEventDestroy(h->ev_stop[c][i]);
     }
+  dolg_slab_release(h);
   delete h;
   return RR_OK;
 }

@@ -328,4 +328,7 @@ hipError_t launch_lpp(const GemmArgs& g, hipStream_t s, int n_cu);
 bool lpp3_eligible(const GemmArgs& g);
 hipError_t launch_lpp3(const GemmArgs& g, hipStream_t s, int n_cu);
 
+// dolg_ops.hip: frees the partial-slab buffers rr_dolg_local_pool keeps for h
+void dolg_slab_release(rr_handle_s* h);
+
 }  // namespace rr

@@ -74,7 +74,7 @@ class ResNet:
         w, b = self.convs[name]
         return ops.conv2d(x, w, b, stride, pad, residual, relu)
 
-    def _forward_h2(self, x, return_x3, hook=None):
+    def _forward_h2(self, x, return_x3, hook=None, return_x3_amax=False):
         """The trunk on the f16x2 core: every conv reads its input's max-|x|
         record and writes its output's (one zeroed [2 + 3 blocks, 64] tensor per
         forward); the max-pool output reuses the stem's record (every stem
@@ -84,7 +84,10 @@ class ResNet:
         first block runs conv3 and its downsample projection as one GEMM
         (ops.bottleneck_out_h2), so the projected identity never reaches HBM.
         hook(i), if given, is called after the i-th conv launch (i = 0: the
-        stem) -- the point where a caller can record a stream event."""
+        stem) -- the point where a caller can record a stream event.
+        return_x3_amax (with return_x3): also return x3's max-|x| record, which
+        its conv3 published, for a caller that runs another f16x2 conv on x3:
+        (x3, x4, record)."""
         cv, h2 = self.convs, self.convs_h2
         hook = hook or (lambda i: None)
         rec = ops.amax_records(2 + 3 * sum(self.layers), x.device)
@@ -95,7 +98,7 @@ class ResNet:
             x = ops.conv2d_h2(x, rec[0], h2["conv1"], cv["conv1"][1], 2, 3, None, True, rec[1])
             x = ops.maxpool2d(x, 3, 2, 1)
         hook(0)
-        xa, r, x3, ci = rec[1], 2, None, 1
+        xa, r, x3, x3a, ci = rec[1], 2, None, None, 1
         for li, nb in enumerate(self.layers):
             for bi in range(nb):
                 p = f"layer{li + 1}.{bi}"
@@ -116,17 +119,22 @@ class ResNet:
                 ci += 3
                 xa, r = rec[r + 2], r + 3
             if li == 2:
-                x3 = x
+                x3, x3a = x, xa
+        if return_x3 and return_x3_amax:
+            return x3, x, x3a
         return (x3, x) if return_x3 else x
 
-    def forward(self, x, return_x3=False, hook=None):
+    def forward(self, x, return_x3=False, hook=None, return_x3_amax=False):
         """x: NHWC fp32 with 3 channels or 4 (zero 4th channel, preferred).
         return_x3: also return layer3's output, as ResNet_DOLG.forward's
-        (x3, x4) (networks/backbone.py:236-242)."""
+        (x3, x4) (networks/backbone.py:236-242).  return_x3_amax (f16x2 trunk,
+        with return_x3): (x3, x4, x3's max-|x| record)."""
         if x.shape[-1] == 3:
             x = torch.nn.functional.pad(x, (0, 1))
         if self.conv_math == "h2":
-            return self._forward_h2(x.contiguous(), return_x3, hook)
+            return self._forward_h2(x.contiguous(), return_x3, hook, return_x3_amax)
+        if return_x3_amax:
+            raise ValueError("return_x3_amax: only the f16x2 trunk (conv_math='h2') keeps max-|x| records")
         x = self._conv(x, "conv1", 2, 3, True)
         x = ops.maxpool2d(x, 3, 2, 1)
         x3 = None
@@ -268,6 +276,79 @@ class GeM(_Extractor):
         f = self.backbone(x_nhwc, hook=hook)
         f = self.pooling(f)
         f = ops.linear(f, self.whiten_w, self.whiten_b)
+        return ops.l2_normalize(f, EPS_L2, out=f)
+
+
+class DOLG(_Extractor):
+    """DOLG (networks/RetrievalNet.py:367-431, forward_test; local branch
+    SpatialAttention2d :433-474): trunk (f3, f4) -> local branch on f3 (1x1
+    conv1 + BN, channel-normalised map weighted by softplus(conv2(relu)))
+    and global branch fc_t(gem_3(f4)) -> the local map's component orthogonal
+    to the global vector, average-pooled -> fc(cat) -> F.normalize.
+
+    The projection is linear in the local map, so fo = m - fg (fg . m) /
+    (fg . fg) with m the local map's spatial mean: rr_dolg_local_pool reads
+    the conv1+BN map once and writes m, rr_dolg_orth_fuse builds [fg | fo];
+    the local map and its projection are never stored ("DOLG").
+
+    Constructor as the reference's (pretrained, with_aspp, backbone) plus
+    state_dict (trunk keys as networks.ResNet accepts, head keys as
+    weights.dolg_head_from_state_dict), seed (synthetic weights when
+    state_dict is None), device, conv_math and stride_on ("3x3" = the
+    reference's torchvision trunk, ResNet_STAGE45; "1x1" for a ResNet_DOLG /
+    MSRA-layout checkpoint).  with_aspp=True (dilated 3x3 convs) and
+    pretrained downloads are not supported."""
+
+    in_channels = 4
+
+    def __init__(self, pretrained=None, with_aspp=False, backbone="resnet101", state_dict=None, seed=0,
+                 device="cuda", conv_math="h2", stride_on="3x3"):
+        if with_aspp:
+            raise ValueError("networks.DOLG: with_aspp=True is not supported (ASPP needs dilated 3x3 convs)")
+        if pretrained is not None:
+            raise ValueError("networks.DOLG: pretrained weights cannot be downloaded; pass state_dict")
+        self.device = torch.device(device)
+        if state_dict is None:
+            head = W.dolg_head_from_state_dict(W.synthetic_dolg_head(seed + 1))
+        else:
+            head = W.dolg_head_from_state_dict(state_dict)
+        self.globalmodel = ResNet(backbone, state_dict, seed, device, conv_math, stride_on)
+        cin = self.globalmodel.outputdim_block4
+        if tuple(head["conv1_w"].shape[1:]) != (1, 1, cin) or head["fc_t_w"].shape[1] != ResNet.outputdim_block5 or \
+                head["fc_t_w"].shape[0] != head["conv1_w"].shape[0] or head["fc_w"].shape[1] != 2 * head["conv1_w"].shape[0]:
+            raise ValueError("networks.DOLG: head weight shapes do not fit the trunk")
+        self.conv_math = conv_math
+        self.pool_g = gem(3.0)
+        self.conv1_w = head["conv1_w"].to(self.device)
+        self.conv1_b = head["conv1_b"].to(self.device)
+        self.conv1_h2 = ops.H2Conv(self.conv1_w) if conv_math == "h2" else None
+        self.conv2_w = head["conv2_w"].to(self.device)
+        self.conv2_b = head["conv2_b"]
+        self.fc_t = (head["fc_t_w"].to(self.device), head["fc_t_b"].to(self.device))
+        self.fc = (head["fc_w"].to(self.device), head["fc_b"].to(self.device))
+        self.outputdim = head["fc_w"].shape[0]
+        self.meta = {"outputdim": self.outputdim}
+
+    def local_mean(self, x3, x3_amax=None):
+        """m [B,1024]: the spatial mean of SpatialAttention2d's output on x3."""
+        if self.conv_math == "h2":
+            y = ops.conv2d_h2(x3, x3_amax, self.conv1_h2, self.conv1_b, 1, 0, None, False)
+        else:
+            y = ops.conv2d(x3, self.conv1_w, self.conv1_b, 1, 0, None, False)
+        return ops.dolg_local_pool(y, self.conv2_w, self.conv2_b)
+
+    def forward_test_nhwc(self, x_nhwc, hook=None):
+        if self.conv_math == "h2":
+            x3, x4, x3a = self.globalmodel(x_nhwc, return_x3=True, hook=hook, return_x3_amax=True)
+        else:
+            (x3, x4), x3a = self.globalmodel(x_nhwc, return_x3=True), None
+        return self.head(x3, x4, x3a)
+
+    def head(self, x3, x4, x3_amax=None):
+        """Everything after the trunk: (x3, x4) NHWC -> descriptors [B,512]."""
+        m = self.local_mean(x3, x3_amax)
+        fg = ops.linear(self.pool_g(x4), *self.fc_t)
+        f = ops.linear(ops.dolg_orth_fuse(fg, m), *self.fc)
         return ops.l2_normalize(f, EPS_L2, out=f)
 
 

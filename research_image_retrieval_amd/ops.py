@@ -304,6 +304,39 @@ def l2_normalize(x, eps=1e-12, out=None):
     return y
 
 
+def dolg_local_pool(y_nhwc, w2, b2):
+    """DOLG local branch after conv1+BN (rr_dolg_local_pool): y [B,H,W,C] (or
+    [B,HW,C], pre-ReLU), conv2 weight w2 [C] and bias b2 (python float) ->
+    m [B,C] = mean_p softplus(w2 . relu(y_p) + b2) y_p / max(||y_p||, 1e-12)."""
+    _f32(y_nhwc, "dolg_local_pool y")
+    _f32(w2, "dolg_local_pool w2")
+    dev = _dev(y_nhwc)
+    b, c = y_nhwc.shape[0], y_nhwc.shape[-1]
+    if w2.numel() != c:
+        raise ValueError(f"dolg_local_pool: w2 has {w2.numel()} weights for {c} channels")
+    hw = y_nhwc.numel() // (b * c) if b * c else 1
+    out = torch.empty((b, c), dtype=torch.float32, device=y_nhwc.device)
+    hd = _lib.handle(dev)
+    _lib.check(_lib.lib().rr_dolg_local_pool(hd, _ptr(y_nhwc), b, hw, c, _ptr(w2), float(b2), _ptr(out), _stream(dev)),
+               hd, "rr_dolg_local_pool")
+    return out
+
+
+def dolg_orth_fuse(fg, m):
+    """[fg | m - fg (fg . m) / (fg . fg)]: fg, m [B,C] -> [B,2C] (rr_dolg_orth_fuse)."""
+    _f32(fg, "dolg_orth_fuse fg")
+    _f32(m, "dolg_orth_fuse m")
+    if fg.dim() != 2 or tuple(fg.shape) != tuple(m.shape):
+        raise ValueError("dolg_orth_fuse: fg and m must both be [B,C]")
+    dev = _dev(fg)
+    b, c = fg.shape
+    out = torch.empty((b, 2 * c), dtype=torch.float32, device=fg.device)
+    hd = _lib.handle(dev)
+    _lib.check(_lib.lib().rr_dolg_orth_fuse(hd, _ptr(fg), _ptr(m), b, c, _ptr(out), _stream(dev)), hd,
+               "rr_dolg_orth_fuse")
+    return out
+
+
 def cosine_topk_workspace_size(nq, n, d, k):
     return int(_lib.lib().rr_cosine_topk_workspace_size(int(nq), int(n), int(d), int(k)))
 

@@ -187,6 +187,75 @@ def fold_bn(conv_w, bn, eps=BN_EPS):
     return wf, bf
 
 
+# ---- DOLG head (networks/RetrievalNet.py:367-474, with_aspp=False) ----------
+DOLG_HEAD_KEYS = tuple(f"localmodel.{k}" for k in (
+    "conv1.weight", "conv1.bias", "bn.weight", "bn.bias", "bn.running_mean", "bn.running_var", "conv2.weight",
+    "conv2.bias")) + ("fc_t.weight", "fc_t.bias", "fc.weight", "fc.bias")
+
+
+def dolg_head_from_state_dict(sd, eps=BN_EPS):
+    """The DOLG head of a reference checkpoint (keys localmodel.conv1.*,
+    localmodel.bn.*, localmodel.conv2.*, fc_t.*, fc.*; a leading ``module.``
+    is dropped; trunk and ArcFace keys are ignored) as fp32 tensors:
+
+      conv1_w [1024,1,1,1024] NHWC-ready, conv1_b [1024]: SpatialAttention2d's
+        conv1 with its eval-mode BN folded in, the conv's OWN bias included
+        (b' = (b_conv - mean) * scale + beta; fold_bn assumes a bias-free
+        conv), computed in float64 and rounded once;
+      conv2_w [1024], conv2_b (python float); fc_t_w [1024,2048], fc_t_b;
+      fc_w [512,2048], fc_b.
+
+    ASPP weights (localmodel.aspp.*, with_aspp=True) raise ValueError: the
+    dilated 3x3 branch is not implemented."""
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
+    if any(k.startswith("localmodel.aspp.") for k in sd):
+        raise ValueError("DOLG checkpoint has localmodel.aspp.* weights (with_aspp=True), which is not supported")
+    missing = [k for k in DOLG_HEAD_KEYS if k not in sd]
+    if missing:
+        raise ValueError(f"DOLG head: missing keys {missing}")
+    w1 = sd["localmodel.conv1.weight"]
+    cout = w1.shape[0]
+    if w1.dim() != 4 or tuple(w1.shape[2:]) != (1, 1):
+        raise ValueError(f"localmodel.conv1.weight: expected [Cout,Cin,1,1], got {tuple(w1.shape)}")
+    g, b = sd["localmodel.bn.weight"].double(), sd["localmodel.bn.bias"].double()
+    m, v = sd["localmodel.bn.running_mean"].double(), sd["localmodel.bn.running_var"].double()
+    scale = g / torch.sqrt(v + eps)
+    wf = (w1.double() * scale[:, None, None, None]).permute(0, 2, 3, 1).contiguous().float()
+    bf = ((sd["localmodel.conv1.bias"].double() - m) * scale + b).float()
+    w2 = sd["localmodel.conv2.weight"]
+    if w2.numel() != cout:
+        raise ValueError(f"localmodel.conv2.weight: expected {cout} weights, got {tuple(w2.shape)}")
+    return {"conv1_w": wf, "conv1_b": bf.contiguous(),
+            "conv2_w": w2.reshape(cout).float().contiguous(), "conv2_b": float(sd["localmodel.conv2.bias"].reshape(())),
+            "fc_t_w": sd["fc_t.weight"].float().contiguous(), "fc_t_b": sd["fc_t.bias"].float().contiguous(),
+            "fc_w": sd["fc.weight"].float().contiguous(), "fc_b": sd["fc.bias"].float().contiguous()}
+
+
+def synthetic_dolg_head(seed, c=1024, c4=2048, out_dim=512):
+    """Seeded DOLG head weights under the reference's keys (DOLG_HEAD_KEYS):
+    non-trivial BN statistics, a conv1 gain that makes the BN output O(1) on
+    the seeded trunk's x3, and a conv2 scale (std 0.05, bias 0.1) that spreads
+    the attention (0.34-0.62 on tests/golden/dolg.npz's inputs).  The fixture
+    generator loads them into the
+    reference's modules; the tests fold them (dolg_head_from_state_dict)."""
+    rs = np.random.RandomState(seed)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
+    sd = collections.OrderedDict()
+    sd["localmodel.conv1.weight"] = t(rs.standard_normal((c, c, 1, 1)) * (4.0 / np.sqrt(c)))
+    sd["localmodel.conv1.bias"] = t(rs.standard_normal(c) * 0.1)
+    sd["localmodel.bn.weight"] = t(rs.uniform(0.5, 1.5, c))
+    sd["localmodel.bn.bias"] = t(rs.standard_normal(c) * 0.1)
+    sd["localmodel.bn.running_mean"] = t(rs.standard_normal(c) * 0.1)
+    sd["localmodel.bn.running_var"] = t(rs.uniform(0.5, 1.5, c))
+    sd["localmodel.conv2.weight"] = t(rs.standard_normal((1, c, 1, 1)) * 0.05)
+    sd["localmodel.conv2.bias"] = t(np.full(1, 0.1))
+    sd["fc_t.weight"] = t(rs.uniform(-1, 1, (c, c4)) / np.sqrt(c4))
+    sd["fc_t.bias"] = t(rs.uniform(-1, 1, c) / np.sqrt(c4))
+    sd["fc.weight"] = t(rs.uniform(-1, 1, (out_dim, 2 * c)) / np.sqrt(2 * c))
+    sd["fc.bias"] = t(rs.uniform(-1, 1, out_dim) / np.sqrt(2 * c))
+    return sd
+
+
 def folded_resnet(sd, arch):
     """torchvision-keyed trunk -> ordered list of folded (name, w, b, stride, pad)."""
     def bn(prefix):

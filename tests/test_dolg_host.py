@@ -1,0 +1,144 @@
+"""DOLG without a GPU: the new C-ABI entries, the head-weight loader, and the
+torch restatement (tests/dolg_ref.py) pinned to the reference's own
+DOLG.forward_test output (tests/golden/dolg.npz, make_golden_dolg.py)."""
+import collections
+import ctypes
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from research_image_retrieval_amd import _lib
+from research_image_retrieval_amd import weights as W
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLD = os.path.join(HERE, "golden")
+sys.path.insert(0, GOLD)
+sys.path.insert(0, HERE)
+import dolg_ref  # noqa: E402
+
+TAGS = ("b2_224", "b1_odd")
+
+
+@pytest.fixture(scope="module")
+def fx():
+    return np.load(os.path.join(GOLD, "dolg.npz"))
+
+
+@pytest.fixture(scope="module")
+def head(fx):
+    return W.dolg_head_from_state_dict(W.synthetic_dolg_head(int(fx["head_seed"])))
+
+
+def test_symbols_and_abi():
+    L = ctypes.CDLL(_lib.LIB_PATH)
+    for name in ("rr_dolg_local_pool", "rr_dolg_orth_fuse"):
+        assert hasattr(L, name) and name in _lib.SIGNATURES
+    L = _lib.lib()
+    assert L.rr_abi_version() == 7 == _lib.ABI_VERSION
+    assert L.rr_dolg_local_pool(None, None, 1, 1, 256, None, 0.0, None, None) == _lib.RR_EINVAL
+    assert L.rr_dolg_orth_fuse(None, None, None, 1, 256, None, None) == _lib.RR_EINVAL
+
+
+@pytest.mark.parametrize("tag", TAGS)
+def test_restatement_tail_reproduces_fixture(fx, head, tag):
+    """From the reference's saved fg and m: the per-pixel projection sequence on
+    a one-pixel map gives fo, and fc + normalize give the descriptor."""
+    fg = torch.from_numpy(fx[tag + "_fg"])
+    m = torch.from_numpy(fx[tag + "_m"])
+    fo = dolg_ref.orth_pool(fg.double(), m.double().unsqueeze(1))
+    ref_fo = fx[tag + "_fo"]
+    err_fo = np.abs(fo.numpy() - ref_fo).max()
+    out = dolg_ref.tail(fg.double(), fo, head)
+    err = np.abs(out.numpy() - fx[tag + "_out"]).max()
+    print(tag, "fo err", err_fo, "rel", err_fo / np.linalg.norm(ref_fo, axis=1).min(), "descriptor err", err)
+    assert err_fo <= 1e-6 * np.linalg.norm(ref_fo, axis=1).min()
+    assert err <= 1e-6
+    # the orthogonal component really was removed, and it was not nothing
+    cos = torch.nn.functional.cosine_similarity(fo, fg.double()).abs().max().item()
+    assert cos < 1e-5
+
+
+def test_restatement_head_reproduces_fixture(fx, head):
+    """The whole head, with conv1 + BN folded by dolg_head_from_state_dict, on
+    the reference trunk's saved (x3, x4) of the odd-size case."""
+    tr = np.load(os.path.join(GOLD, "resnet_dolg.npz"))
+    assert int(tr["weight_seed"]) == int(fx["weight_seed"])
+    assert list(tr["b1_odd_case"]) == list(fx["b1_odd_case"])
+    got = dolg_ref.head_forward(torch.from_numpy(tr["b1_odd_x3"]), torch.from_numpy(tr["b1_odd_x4"]), head,
+                                dtype=torch.float64)
+    err = np.abs(got["out"].numpy() - fx["b1_odd_out"]).max()
+    ref_m = fx["b1_odd_m"]
+    err_m = np.abs(got["m"].numpy() - ref_m).max() / np.linalg.norm(ref_m, axis=1).min()
+    err_att = np.abs(got["att"].numpy() - fx["b1_odd_att"][:, 0]).max()
+    print("descriptor err", err, "m rel err", err_m, "att err", err_att)
+    assert err <= 1e-6
+    assert err_m <= 1e-6 and err_att <= 1e-5
+    assert np.abs(got["fg"].numpy() - fx["b1_odd_fg"]).max() <= 1e-5 * np.abs(fx["b1_odd_fg"]).max()
+
+
+def _reference_keyed(seed):
+    sd = W.synthetic_dolg_head(seed)
+    sd["localmodel.bn.num_batches_tracked"] = torch.tensor(0)
+    sd["desc_cls.weight"] = torch.zeros(3, 512)            # ArcFace head: ignored
+    sd["globalmodel.stem.conv.weight"] = torch.zeros(64, 3, 7, 7)  # trunk: ignored here
+    return sd
+
+
+@pytest.mark.parametrize("prefix", ["", "module."])
+def test_head_from_state_dict_round_trip(prefix):
+    sd = _reference_keyed(5)
+    h = W.dolg_head_from_state_dict(collections.OrderedDict((prefix + k, v) for k, v in sd.items()))
+    assert h["conv1_w"].shape == (1024, 1, 1, 1024) and h["conv1_b"].shape == (1024,)
+    assert h["conv2_w"].shape == (1024,) and isinstance(h["conv2_b"], float)
+    assert torch.equal(h["conv2_w"], sd["localmodel.conv2.weight"].reshape(-1))
+    assert h["conv2_b"] == float(sd["localmodel.conv2.bias"][0])
+    for k in ("fc_t", "fc"):
+        assert torch.equal(h[k + "_w"], sd[k + ".weight"]) and torch.equal(h[k + "_b"], sd[k + ".bias"])
+    assert h["fc_t_w"].shape == (1024, 2048) and h["fc_w"].shape == (512, 2048)
+    assert all(v.dtype == torch.float32 and v.is_contiguous() for v in h.values() if isinstance(v, torch.Tensor))
+
+
+def test_head_fold_includes_conv_bias():
+    """bn(conv1(x)) evaluated in float64 from the unfolded weights equals the
+    folded conv to fp32 rounding of the folded weights; dropping the conv's
+    own bias (what fold_bn would do) is far outside that."""
+    sd = W.synthetic_dolg_head(6)
+    h = W.dolg_head_from_state_dict(sd)
+    rs = np.random.RandomState(0)
+    x = torch.from_numpy(rs.standard_normal((7, 1024)))
+    w, b = sd["localmodel.conv1.weight"].double().reshape(1024, 1024), sd["localmodel.conv1.bias"].double()
+    g, beta = sd["localmodel.bn.weight"].double(), sd["localmodel.bn.bias"].double()
+    mu, var = sd["localmodel.bn.running_mean"].double(), sd["localmodel.bn.running_var"].double()
+    ref = (x @ w.t() + b - mu) / torch.sqrt(var + 1e-5) * g + beta
+    got = x @ h["conv1_w"].double().reshape(1024, 1024).t() + h["conv1_b"].double()
+    scale = g / torch.sqrt(var + 1e-5)
+    # one fp32 rounding per folded weight (2^-24 relative) over a 1024-term dot product, and of the bias
+    bound = 2.0 ** -24 * ((x.abs() @ (w * scale[:, None]).abs().t()) + (ref.abs() + 1))
+    assert bool(((got - ref).abs() <= bound).all())
+    bias64 = (b - mu) * scale + beta
+    assert torch.equal(h["conv1_b"], bias64.float())
+    no_bias = (beta - mu * scale).float()
+    assert (h["conv1_b"] - no_bias).abs().max().item() > 1e-2
+
+
+def test_head_rejects_aspp_and_missing_keys():
+    sd = W.synthetic_dolg_head(7)
+    bad = dict(sd)
+    bad["localmodel.aspp.aspp.0.weight"] = torch.zeros(512, 1024, 1, 1)
+    with pytest.raises(ValueError, match="aspp"):
+        W.dolg_head_from_state_dict(bad)
+    bad = dict(sd)
+    bad.pop("fc_t.bias")
+    with pytest.raises(ValueError, match="fc_t.bias"):
+        W.dolg_head_from_state_dict(bad)
+
+
+def test_dolg_rejects_aspp_and_pretrained_without_gpu():
+    from research_image_retrieval_amd.networks import DOLG
+    with pytest.raises(ValueError, match="with_aspp"):
+        DOLG(with_aspp=True)
+    with pytest.raises(ValueError, match="pretrained"):
+        DOLG(pretrained="v1")
