@@ -105,7 +105,7 @@ int rr_get_device(rr_handle_t h, int* device);
  *                     4 (256x320 for bf16 filter / score sweeps, 256x256 otherwise),
  *                     5 (bf16 sweeps with K % 128 == 0, fp8 sweeps with K % 256 == 0:
  *                     256x256 8-phase pipeline; otherwise as 3)
- *   RR_TUNE_S3_CFG:   f16x2 split core, 1..15 (gemm_s3.hip tile table; 13 = the halo-staged stride-1 3x3 tile on
+ *   RR_TUNE_S3_CFG:   f16x2 split core, 1..15 (h2_tile.hip tile table; 13 = the halo-staged stride-1 3x3 tile on
  *                     v_mfma_f32_32x32x16_f16, 14 = the same on v_mfma_f32_16x16x32_f16
  *                     (the default picks 14's form for cout % 256 == 0, 13's for cout 64);
  *                     15 = the 256x256 tile (12) as a persistent k-stream (the default
@@ -338,7 +338,7 @@ int rr_resize_bilinear(rr_handle_t h, const float* x, int b, int hgt, int wid,
                        int c, int out_h, int out_w, float inv_scale_h,
                        float inv_scale_w, float* y, void* stream);
 
-/* fp32-accurate convolution on the fp16 matrix cores (gemm_s3.hip, f16x2
+/* fp32-accurate convolution on the fp16 matrix cores (h2_*.hip, the f16x2
  * split): the same operation, layouts and epilogue as rr_conv2d on the
  * 16-bit MFMA at three fp16 products per fp32 product.  Every fp32 operand is scaled by a power of two and split
  * into two fp16 pieces, x 2^e = x0 + x1 + r with |r| <= 2^-22 |x 2^e|; a.b

@@ -1,5 +1,5 @@
 // gemm_epilogue.hpp — the stored-C epilogue shared by the GEMM kernels
-// (gemm_f32.hip, gemm_s3.hip): bias, residual, ReLU / QuickGELU, fp32 or
+// (gemm_f32.hip, h2_*.hip): bias, residual, ReLU / QuickGELU, fp32 or
 // bf16 output, written as whole rows through an LDS-staged tile.
 #pragma once
 
@@ -88,7 +88,7 @@ __device__ __forceinline__ f32x4 ln_row_stats(const float* st, long long m, int 
   return r;
 }
 
-// ---- f16x2 split scales (gemm_s3.hip, SP 2) ----
+// ---- f16x2 split scales (h2_*.hip) ----
 // A tensor's max |x| lives in RR_AMAX_SLOTS words (float bit patterns of
 // non-negative values, so unsigned order = float order), each the max over
 // the waves that hashed to it: no single hot address.  Non-finite values are

@@ -13,7 +13,7 @@
 // The epilogue goes in four 64-row slabs (slab s = MFMA row tile s of every
 // wave, all eight waves staging each) through the stage its last k-tile
 // released; with a residual, each 32-row band's residual rows are loaded two
-// bands ahead (as config 15 of gemm_s3.hip).  Same fragments, k-step order
+// bands ahead (as config 15, h2_stream256.hip).  Same fragments, k-step order
 // and per-accumulator MFMA sequence (v_mfma_f32_16x16x32_bf16, one per
 // sub-tile per 32-deep k-step, k-steps in order) and the same epilogue
 // arithmetic (store_slab) as the one-tile kernel: bit-identical results.
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(512, 1) void gemm_lpp_kernel(GemmArgs g, int tiles_
   const int nk = g.K / EPR;
   const int my_tiles = (ntiles - bid + G - 1) / G;
   const int J = my_tiles * nk;
-  // local tile tl -> origin (as gemm_s3.hip config 8 / 15: virtual block
+  // local tile tl -> origin (as the split core's config 8 / 15: virtual block
   // bid + tl G keeps the block's XCD, then the bijective XCD remap)
   auto tile_origin = [&](int tl, int& m0, int& n0) __attribute__((always_inline)) {
     const int v = bid + tl * G;

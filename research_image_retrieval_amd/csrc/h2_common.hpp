@@ -1,8 +1,9 @@
-// h2_common.hpp — pieces of the split-core GEMM kernels (gemm_s3.hip):
-// vector types, the f16x2 MFMA wrappers (and the retired bf16x3 ones the
-// SP-templated kernels still name), the f16x2
-// split of an 8-k chunk, the plane-row slot swizzle and the asynchronous
-// (inline-asm) A loads with their register laundering.
+// h2_common.hpp — pieces shared by the f16x2 split-core GEMM kernel files
+// (h2_tile.hip, h2_stream.hip, h2_stream256.hip, h2_halo.hip, h2_stem.hip):
+// the epilogue flag-set dispatch, the zero page, the diagnostic phase timers,
+// vector types, the fp16 MFMA wrappers, the f16x2 split of an 8-k chunk, the
+// plane-row slot swizzle and the asynchronous (inline-asm) A loads with their
+// register laundering.
 #pragma once
 
 #include "gemm_epilogue.hpp"
@@ -14,38 +15,41 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
-// Split kinds (template SP = planes per operand):
-//   3: bf16 x3 (gemm_s3.hip header), six bf16 MFMAs per product;
-//   2: fp16 x2 at a power-of-two scale, three fp16 MFMAs per product.  An
-//      operand scaled so its max |x| lies in [2^14, 2^15) (h2_exp) splits as
-//      x 2^e = x0 + x1 + r, x0 = RNE16(x 2^e), x1 = RNE16(x 2^e - x0) (the
-//      difference is exact in fp32), |r| <= 2^-22 |x 2^e|: fp16 carries 11
-//      significant bits to bf16's 8, so two pieces hold 22 bits.  a.b keeps
-//      a0b0 (own accumulator) + a0b1 + a1b0; dropped: a1b1 and the two
-//      remainders, each <= 2^-22 |a||b| with random sign, so their sum over a
-//      long dot product stays below the fp32 accumulation's own rounding.
-//      Products of fp16 pieces are exact in the fp32 accumulator, and the
-//      scales are powers of two: the epilogue's acc * 2^-(ea + eb_n) is exact.
-//      Values below 2^-18 of their tensor's max lose relative precision (an
-//      absolute error <= 2^-40 of that max).  Same k-loop, LDS layout and
-//      epilogues as SP 3 with two planes per operand instead of three.
-template <int SP>
-struct S3Frag {
-  typedef bf16x8 T;
-};
-template <>
-struct S3Frag<2> {
-  typedef f16x8 T;
-};
-template <int SP>
-__device__ __forceinline__ f32x4 s3_mf16(const typename S3Frag<SP>::T& a, const typename S3Frag<SP>::T& b, f32x4 c) {
-  if constexpr (SP == 2) return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+// Epilogue flag sets of the split core: the scale, the max-|C| record (skipped
+// at run time when c_amax is NULL) and the bias (zeros when NULL) always
+// compiled in; residual and ReLU select the instance.
+constexpr int H2_EP = EP_SCALE | EP_AMAX | EP_BIAS;
+// Calls f with the flag set of g's residual / ReLU pair as a
+// std::integral_constant (f names the kernel instance from it).  SC1: an
+// instance with a residual also streams it (EP_SC1).
+template <bool SC1, class F>
+inline hipError_t h2_ep_dispatch(const GemmArgs& g, F&& f) {
+  constexpr int RES = EP_RES | (SC1 ? EP_SC1 : 0);
+  switch (ep_flags(g) & (EP_RES | EP_RELU)) {
+    case EP_RELU: return f(std::integral_constant<int, H2_EP | EP_RELU>{});
+    case EP_RES | EP_RELU: return f(std::integral_constant<int, H2_EP | RES | EP_RELU>{});
+    case EP_RES: return f(std::integral_constant<int, H2_EP | RES>{});
+    default: return f(std::integral_constant<int, H2_EP>{});
+  }
 }
-template <int SP>
-__device__ __forceinline__ f32x16 s3_mf32(const typename S3Frag<SP>::T& a, const typename S3Frag<SP>::T& b, f32x16 c) {
-  if constexpr (SP == 2) return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+
+// The split: fp16 x2 at a power-of-two scale, three fp16 MFMAs per product,
+// two planes per operand.  An operand scaled so its max |x| lies in
+// [2^14, 2^15) (h2_exp) splits as x 2^e = x0 + x1 + r, x0 = RNE16(x 2^e),
+// x1 = RNE16(x 2^e - x0) (the difference is exact in fp32),
+// |r| <= 2^-22 |x 2^e|: fp16 carries 11 significant bits, so two pieces hold
+// 22.  a.b keeps a0b0 (own accumulator) + a0b1 + a1b0; dropped: a1b1 and the
+// two remainders, each <= 2^-22 |a||b| with random sign, so their sum over a
+// long dot product stays below the fp32 accumulation's own rounding.
+// Products of fp16 pieces are exact in the fp32 accumulator, and the scales
+// are powers of two: the epilogue's acc * 2^-(ea + eb_n) is exact.  Values
+// below 2^-18 of their tensor's max lose relative precision (an absolute
+// error <= 2^-40 of that max).
+__device__ __forceinline__ f32x4 s3_mf16(const f16x8& a, const f16x8& b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 s3_mf32(const f16x8& a, const f16x8& b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
 
 // fp16 x2 split of 8 fp32 values (one 8-k chunk) at scale sc into two packed
@@ -68,17 +72,14 @@ __device__ __forceinline__ void split2h8(const f32x4 (&r)[2], float sc, u32x4& p
 // 16 consecutive lanes.  BK = 32 (64-B rows, 4 slots; a row's bank quad is
 // 4 (row & 3) + slot): slot ^ (2 ((row >> 3) & 1) + ((row >> 4) & 1)) is
 // conflict-free for both fragment reads, 16x16x32 (lane l: row l & 15, slot
-// l >> 4) and 32x32x16 (row l & 31, slot 2 step + (l >> 5)) — the earlier
-// slot ^ ((row >> 2) & 3) was 2-way on every 16x16x32 read (checked by
+// l >> 4) and 32x32x16 (row l & 31, slot 2 step + (l >> 5)) — a plain
+// slot ^ ((row >> 2) & 3) is 2-way on every 16x16x32 read (checked by
 // enumeration, tools/lds_swizzle_check.py).  BK = 16 (32-B rows, 2 slots):
 // slot ^ ((row >> 3) & 1).  ds_write_b128 groups (8 contiguous lanes = two
-// rows) are conflict-free under any per-row permutation.  The bf16x3 split
-// (SP 3) keeps the earlier form: its config-4 conv kernels sit at the register
-// limit and the new one's address arithmetic spilled them.
-template <int BK, int SP>
+// rows) are conflict-free under any per-row permutation.
+template <int BK>
 __device__ __forceinline__ int pswz(int row, int slot) {
-  if constexpr (BK == 32 && SP == 2) return slot ^ ((((row >> 3) & 1) << 1) | ((row >> 4) & 1));
-  else if constexpr (BK == 32) return slot ^ ((row >> 2) & 3);
+  if constexpr (BK == 32) return slot ^ ((((row >> 3) & 1) << 1) | ((row >> 4) & 1));
   else return slot ^ ((row >> 3) & 1);
 }
 
@@ -123,6 +124,61 @@ __device__ __forceinline__ int s3_opaque(int v) {
   asm volatile("" : "+v"(v));
   return v;
 }
+
+// 32 zero bytes in global memory: the A source of padding taps and rows past
+// M (one copy per kernel file: no relocatable device code)
+[[maybe_unused]] static __device__ f32x4 s3_zero_src[2];
+__device__ __forceinline__ const f32x4* s3_zero_page() { return s3_zero_src; }
+
+// Diagnostic build only (-DRR_S3_PHASES=1 on every h2_*.hip,
+// tools/phase_build.sh): per-wave s_memtime deltas of the k-loop phases,
+// summed over every wave into the kernel file's s3_phase_sum[phase]; the
+// file's <name>_phases() reads and clears it and rr_debug_phases
+// (h2_dispatch.hip) gathers the rows: 0 h2_tile.hip, 1 h2_stream.hip,
+// 2 h2_stream256.hip, 3 h2_halo.hip.
+// Phases: 0 issue loads, 1 first MFMA part, 2 mid wait, 3 split + second
+// MFMA part, 4 end wait, 5 barrier, 6 epilogue, 7 prologue (rows 0 and 1).
+// Row 2 (config 15): 0 issue + first k-step, 1 mid wait, 2 split + second
+// k-step, 3 end wait + barrier, 4 epilogue staging (+ its barrier), 5
+// epilogue residual waits, 6 epilogue stores (+ barriers), 7 prologue.  Row 3
+// (the halo tile): 0 B DMA + halo pass issue / split, 1 MFMAs (+ fragment
+// reads), 2 end wait, 3 barrier, 6 epilogue, 7 prologue.  The timers cost a
+// few % and are compiled out of the product library.
+#ifndef RR_S3_PHASES
+#define RR_S3_PHASES 0
+#endif
+#if RR_S3_PHASES
+[[maybe_unused]] static __device__ unsigned long long s3_phase_sum[8];
+struct S3Phases {
+  unsigned long long t, acc[8];
+  __device__ __forceinline__ S3Phases() {
+    t = __builtin_amdgcn_s_memtime();
+    for (int i = 0; i < 8; ++i) acc[i] = 0;
+  }
+  __device__ __forceinline__ void mark(int i) {
+    const unsigned long long n = __builtin_amdgcn_s_memtime();
+    acc[i] += n - t;
+    t = n;
+  }
+  __device__ __forceinline__ void flush() {
+    if ((threadIdx.x & 63) == 0)
+      for (int i = 0; i < 8; ++i) atomicAdd(&s3_phase_sum[i], acc[i]);
+  }
+};
+// the body of a kernel file's <name>_phases(out[8])
+[[maybe_unused]] static int s3_phases_take(unsigned long long* out) {
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(s3_phase_sum), sizeof(s3_phase_sum)) != hipSuccess) return RR_EHIP;
+  const unsigned long long z[8] = {};
+  return hipMemcpyToSymbol(HIP_SYMBOL(s3_phase_sum), z, sizeof(z)) == hipSuccess ? RR_OK : RR_EHIP;
+}
+#define RR_PH_DECL S3Phases ph_;
+#define RR_PH(i) ph_.mark(i)
+#define RR_PH_FLUSH() ph_.flush()
+#else
+#define RR_PH_DECL
+#define RR_PH(i) ((void)0)
+#define RR_PH_FLUSH() ((void)0)
+#endif
 
 
 }  // namespace rr

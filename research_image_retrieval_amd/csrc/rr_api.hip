@@ -537,7 +537,7 @@ int rr_conv2d_h2(rr_handle_t h, const float* x, const unsigned* x_amax, int b, i
   g.c_amax = y_amax;
   const bool dense = kh == 1 && kw == 1 && stride == 1 && pad == 0 && cin != 4;
   if (dense) g.lda = cin;
-  return launch_gemm_s3(h, dense ? A_DENSE : (cin == 4 ? A_CONV_C4 : A_CONV), g, (hipStream_t)stream, kTimeGemm, 2);
+  return launch_gemm_s3(h, dense ? A_DENSE : (cin == 4 ? A_CONV_C4 : A_CONV), g, (hipStream_t)stream, kTimeGemm);
 }
 
 int rr_stem_pool_h2(rr_handle_t h, const float* x, const unsigned* x_amax, int b, int hgt, int wid, const void* w2,

@@ -20,8 +20,8 @@ struct rr_handle_s {
     int gemm_cfg = 0;  // fp32 core: 22, 41 or 88
     int gemm_bk = 0;   // fp32 core k-tile depth: 16 or 32
     int lp_cfg = 0;    // bf16 / fp8 core: 1 = 128x128, 2 = 256x64, 3 = 256x256, 4 = 256x320 (filter sweeps), 5 = 8-phase 256x256 (bf16 / fp8 sweeps), 6 = the persistent bf16 tile with three A stages (tests); 0: the pick (the persistent 256x256 bf16 tile for the ViT epilogues, K <= 1024)
-    int s3_cfg = 0;    // split cores: 1..15 (gemm_s3.hip tile table; 9-15 f16x2 only); 0: the pick
-    int s3_stagger = -1;  // split-bf16 core round stagger in ~1 us sleeps (-1: the library's pick)
+    int s3_cfg = 0;    // f16x2 split core: 1..15 (h2_tile.hip tile table); 0: the pick
+    int s3_stagger = -1;  // f16x2 split core round stagger in ~1 us sleeps (-1: the library's pick)
     int sweep_mf16 = -1;   // bf16 256x320 filter sweep on v_mfma_f32_16x16x32_bf16 (1) or 32x32x16 (0); -1: the pick (0)
     int sweep_il = -1;     // bf16 256x320 filter sweep: next k-tile's DMA spread among the MFMAs (1) or one burst (0); -1: the pick (1)
     int conv_il = -1;      // f16x2 256x256 conv tile (s3_cfg 12) and halo 16x16x32 tile: next k-tiles' loads spread among the MFMAs (1) or one burst (0); -1: the pick (0)
@@ -200,10 +200,9 @@ struct GemmArgs {
   int k_split = 0;
   long long c_split_stride = 0;
   int sym = 0;  // E_STORE of a symmetric product: skip tiles strictly below the diagonal
-  // split GEMM (gemm_s3.hip): B = three bf16 planes (SP 3) or two fp16 planes
-  // (SP 2), b_plane elements apart
+  // f16x2 split GEMM (h2_*.hip): B = two fp16 planes, b_plane elements apart
   long long b_plane = 0;
-  // f16x2 split (SP 2): B row n was split at scale 2^e_n, col_scale[n] = 2^-e_n;
+  // B row n was split at scale 2^e_n, col_scale[n] = 2^-e_n;
   // A's max |x| is read from a_amax (RR_AMAX_SLOTS words); the epilogue
   // publishes max |C| to c_amax when it is set
   const float* col_scale = nullptr;
@@ -279,10 +278,30 @@ __device__ __forceinline__ void tile_coords(int bid, int nwg, int tiles_n, int& 
 int launch_gemm(rr_handle_s* h, int amode, int emode, const GemmArgs& a, hipStream_t s, int timer_cls,
                 int dt = DT_F32);
 
-// fp32-accurate GEMM on the 16-bit matrix cores (gemm_s3.hip): A fp32
-// (A_DENSE, A_CONV or A_CONV_C4), E_STORE epilogue; sp must be 2: B = fp16
-// planes [2][N][ldb] + col_scale from launch_split2h, A scaled by its a_amax
-int launch_gemm_s3(rr_handle_s* h, int amode, const GemmArgs& g, hipStream_t s, int timer_cls, int sp = 2);
+// fp32-accurate GEMM on the 16-bit matrix cores (the f16x2 split core,
+// h2_dispatch.hip): A fp32 (A_DENSE, A_CONV or A_CONV_C4), E_STORE epilogue;
+// B = fp16 planes [2][N][ldb] + col_scale from launch_split2h, A scaled by
+// its a_amax
+int launch_gemm_s3(rr_handle_s* h, int amode, const GemmArgs& g, hipStream_t s, int timer_cls);
+// The split core's kernel files, as h2_dispatch.hip calls them (arguments
+// checked there; n_cu: the device's CUs, st: the round stagger):
+//  h2_tile.hip: tile config cfg (4, 7, 9-12, any other value 3) on A mode
+//   amode; the implicit-GEMM stem + max-pool (h2_stem.hip's fallback)
+hipError_t launch_h2_tile(int cfg, int amode, const GemmArgs& g, hipStream_t s, int n_cu, int st);
+hipError_t launch_h2_tile_stem_pool(const GemmArgs& q, hipStream_t s, int n_cu);
+//  h2_stream.hip: config 8 (dense A, N % 256 == 0)
+hipError_t launch_s3p(const GemmArgs& g, hipStream_t s, int n_cu, int st);
+//  h2_stream256.hip: config 15 (dense A) where s3q_shape and s3q_fits hold
+bool s3q_shape(const GemmArgs& g);
+bool s3q_fits(const GemmArgs& g);
+hipError_t launch_s3q(const GemmArgs& g, hipStream_t s, int n_cu, int st);
+//  h2_halo.hip: the raster halo tile (hr = h2_halo_rows(g) != 0; mf: the
+//   halo_mf form, pers: the N = 64 persistent stream) and the 2-D block tiles
+//   (where h2_halo_2d_ok)
+int h2_halo_rows(const GemmArgs& g);
+hipError_t launch_h2_halo(const GemmArgs& g, hipStream_t s, int hr, int mf, bool pers, int n_cu);
+bool h2_halo_2d_ok(const GemmArgs& g);
+hipError_t launch_h2_halo_2d(const GemmArgs& g, hipStream_t s);
 // f16x2 two-segment GEMM (GemmArgs A2 / K1): the persistent tile, N % 256 == 0
 int launch_gemm_h2_seg2(rr_handle_s* h, const GemmArgs& g, hipStream_t s, int timer_cls);
 // f16x2 NHWC4 stem conv + ReLU + 3x3/2 pad-1 max-pool (GemmArgs pool_*), N == 64

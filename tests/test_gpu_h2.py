@@ -1,4 +1,4 @@
-"""The f16x2 split core (gemm_s3.hip, SP 2; rr_conv2d_h2): the power-of-two
+"""The f16x2 split core (csrc/h2_*.hip; rr_conv2d_h2): the power-of-two
 scaled 2-way fp16 split, and fp32-grade accuracy of the convolutions it runs,
 measured against float64 next to the exact-fp32 MFMA core and the split-bf16
 core on the same inputs (the bar the retired split-bf16 core's tests set:

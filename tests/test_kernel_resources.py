@@ -2,7 +2,7 @@
 
 The split cores run at the register file's edge (242-256 VGPRs at two waves
 per SIMD) and load through inline asm whose registers the compiler does not
-track (gemm_s3.hip): a spill of such a register before its counted wait would
+track (csrc/h2_*.hip): a spill of such a register before its counted wait would
 read an unloaded value.  This reads the gfx950 code-object metadata of the
 library that ships (tools/kernel_resources.py) and fails if any kernel has a
 private segment (scratch) -- no GPU needed."""
@@ -24,6 +24,7 @@ def test_no_kernel_uses_scratch():
                        capture_output=True, text=True, timeout=120)
     bad = [ln for ln in r.stdout.splitlines() if " scratch " in ln and not ln.split(" scratch ")[1].strip().startswith("0 ")]
     assert r.returncode == 0, "kernels using scratch:\n" + "\n".join(bad) + "\n" + r.stderr[-500:]
-    # the split-core kernels are all there (f16x2 and bf16x3, persistent and tiled)
-    for name in ("gemm_s3p_kernel<", "gemm_s3_kernel<", "split2h_kernel", "amax_kernel"):
+    # the f16x2 split-core kernels are all there (tiled, persistent, halo, stem, and the two helpers)
+    for name in ("gemm_s3p_kernel<", "gemm_s3_kernel<", "gemm_s3q_kernel<", "gemm_h2_halo_kernel<",
+                 "stem_pool_halo_kernel<", "split2h_kernel", "amax_kernel"):
         assert name in r.stdout, name

@@ -1,5 +1,5 @@
 """Enumerates LDS bank quads of the split cores' fragment reads
-(gemm_s3.hip pswz) over gfx950's ds_read_b128 lane groups
+(h2_common.hpp pswz) over gfx950's ds_read_b128 lane groups
 (MI355X_MICROARCH.md, LDS): prints the worst n-way conflict of each read
 pattern for the current and the previous BK = 32 swizzle, and checks that
 ds_write_b128 staging stays conflict-free.  CPU only."""

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Diagnostic librr with the f16x2 kernels' s_memtime phase timers compiled in
-# (-DRR_S3_PHASES=1, gemm_s3.hip) -> ab/librr_phases.so; tools/phase_run.py
+# (-DRR_S3_PHASES=1 on every h2_*.hip) -> ab/librr_phases.so; tools/phase_run.py
 # loads it through RR_LIB_PATH.  Built here (CPU), not on the GPU box.
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -11,7 +11,7 @@ objs=""
 for f in *.hip; do
   o=$B/${f%.hip}.o
   extra=""
-  [ "$f" = gemm_s3.hip ] && extra="-DRR_S3_PHASES=1"
+  case "$f" in h2_*.hip) extra="-DRR_S3_PHASES=1" ;; esac
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result $extra -c $f -o $o &
   objs="$objs $o"
 done
