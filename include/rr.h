@@ -224,7 +224,15 @@ int rr_topk_merge(rr_handle_t h, const float* part_scores,
 /* ---- low-precision search (configs C4 bf16, C5 fp8) ---------------------
  * dtype: 1 = bf16 (RNE), 2 = fp8 OCP e4m3 with one fp32 scale per row.
  * rr_quantize_rows: x [rows][d] fp32 -> y [rows][d] (2 or 1 bytes/elem);
- * fp8 writes row_scale[r] = amax(row)/448 (x ~= q * scale).              */
+ * fp8 writes row_scale[r] = amax(row)/448 (x ~= q * scale).
+ * NaN: bf16 keeps it (a NaN element rounds to a bf16 NaN).  fp8: a row that
+ * holds a NaN element gets row_scale[r] = NaN, so the whole row dequantises
+ * to NaN and every score against it is NaN (rr_cosine_topk_lp multiplies
+ * by the scales; such rows rank last, by index, as in rr_cosine_topk) --
+ * the same as the exact ranker's score of a row with one NaN element.  The
+ * row's amax, and the bytes of its finite elements, are those of its finite
+ * elements; the byte written for a NaN element itself is unspecified.
+ * Rows without a NaN are unaffected.                                        */
 int rr_quantize_rows(rr_handle_t h, const float* x, long long rows, int d,
                      int dtype, void* y, float* row_scale, void* stream);
 

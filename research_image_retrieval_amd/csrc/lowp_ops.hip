@@ -29,14 +29,23 @@ __global__ __launch_bounds__(256) void quantize_rows_kernel(const float* __restr
     if (row_scale != nullptr && lane == 0) row_scale[row] = 1.0f;
     return;
   }
+  // fmaxf skips NaN (and the clamp below turns a NaN element into -448), so a
+  // NaN anywhere in the row is tracked on its own and poisons the row's scale:
+  // every consumer multiplies by it (the GEMM epilogues: acc * s_a * s_b), so
+  // the row dequantises, and scores, as NaN whatever the fp8 MFMA makes of the
+  // bytes.  amax, and with it the bytes of the finite elements, is that of the
+  // finite elements.
   float amax = 0.f;
+  int has_nan = 0;
   for (int i = lane; i < d4; i += 64) {
     const float4 v = xr[i];
     amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+    has_nan |= (v.x != v.x) | (v.y != v.y) | (v.z != v.z) | (v.w != v.w);
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
-  const float scale = amax > 0.f ? amax / kFp8Max : 1.0f;
+  has_nan = __any(has_nan);
+  const float scale = has_nan ? __builtin_nanf("") : (amax > 0.f ? amax / kFp8Max : 1.0f);
   const float inv = amax > 0.f ? kFp8Max / amax : 0.0f;
   int* yr = reinterpret_cast<int*>(reinterpret_cast<uint8_t*>(y) + row * d);
   for (int i = lane; i < d4; i += 64) {
