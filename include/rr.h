@@ -432,14 +432,21 @@ int rr_gem_pool(rr_handle_t h, const float* x, int b, int hw, int c, float p,
 /* y[m][n] = x[m][:] . w[n][:] + bias[n]   (bias may be NULL).
  * Replaces GeM.whiten 1x1 conv (networks/RetrievalNet.py:332,342),
  * GeMModel.feature_proj Linear (models/gem_pooling.py:50,68) and the
- * PCA-whitening ConvDimReduction apply (networks/spca.py:205-227).        */
+ * PCA-whitening ConvDimReduction apply (networks/spca.py:205-227).
+ * Any k and n: with k % 4 == 0 (x and w 16-byte aligned) the rows are staged
+ * as 16-byte units; any other k (a classifier over feature_dim = 130) takes
+ * the scalar gather of the generic convolution, same epilogue, no alignment
+ * requirement.  m = 0 is a no-op.                                          */
 int rr_linear(rr_handle_t h, const float* x, int m, int k, const float* w,
               const float* bias, int n, float* y, void* stream);
 
 /* y = act(x . w^T + bias + residual); act 0 = none, 1 = ReLU, 2 = QuickGELU
  * (x * sigmoid(1.702 x)).  bias / residual ([m][n]) may be NULL.  Replaces the
  * ViT projections of networks/model.py:171-192 (MHA in/out_proj, c_fc +
- * QuickGELU, c_proj + residual) and `ln_post(x[:,0]) @ proj` (:239-241).   */
+ * QuickGELU, c_proj + residual) and `ln_post(x[:,0]) @ proj` (:239-241).
+ * k % 4 == 0 and 16-byte aligned x and w (RR_EINVAL otherwise: the fused
+ * projections have no scalar-gather form); any n, n % 4 != 0 stores per
+ * element.  m = 0 is a no-op.                                              */
 int rr_linear_ex(rr_handle_t h, const float* x, int m, int k, const float* w,
                  const float* bias, int n, const float* residual, int act,
                  float* y, void* stream);

@@ -651,6 +651,27 @@ int rr_amax_f32(rr_handle_t h, const float* x, long long n, unsigned* amax, void
 
 int rr_linear(rr_handle_t h, const float* x, int m, int k, const float* w, const float* bias, int n, float* y,
               void* stream) {
+  if (k > 0 && (k & 3) && x && w && y && m >= 0 && n > 0) {
+    // k % 4 != 0 (a Linear of any width: GeMModel's classifier over a
+    // feature_dim like 130): rows are not whole 16-B units, so the dense
+    // staging cannot read them.  The same product as a 1x1 convolution of m
+    // one-pixel images with k channels on the generic gather (scalar loads
+    // of A and B, any k, no alignment needed) and the same epilogue.
+    RR_ENTRY(h);
+    GemmArgs g;
+    g.A = x;
+    g.M = m;
+    g.K = k;
+    g.H = g.W = g.OH = g.OW = 1;
+    g.Cin = k;
+    g.B = w;
+    g.ldb = k;
+    g.N = n;
+    g.C = y;
+    g.ldc = n;
+    g.bias = bias;
+    return launch_gemm(h, A_CONV_GENERIC, E_STORE, g, (hipStream_t)stream, kTimeGemm);
+  }
   return rr_linear_ex(h, x, m, k, w, bias, n, nullptr, 0, y, stream);
 }
 
