@@ -4,7 +4,7 @@
 // each query's threshold) and the transposed score store of the seed pass.
 // Measured (tools/sweep_ab.py, profiles/r02c_sweep_ab.txt): 1.22-1.25x the
 // 256x320 sweep tile at 256 / 512 / 768 queries x 1.6 M x 2048, 1.03x at 1280;
-// on the ViT linears (K = 768, stored C) it was 2-4 % slower than gemm_f32.hip's
+// on the ViT linears (K = 768, stored C) it was 2-4 % slower than gemm_lp.hip's
 // 256x256 tile, so stored-C GEMMs do not come here.
 //
 // C[M,N] = A[M,K] . B[N,K]^T, bf16 in, fp32 accumulate, K % 128 == 0.
@@ -31,24 +31,21 @@
 // fp8 (OCP e4m3, DT_FP8; the C5 sweep): the same 128-B rows hold 128 k.  A
 // wave's 64x32 piece of a quadrant is two 32x32 tiles on the block-scaled
 // v_mfma_scale_f32_32x32x64_f8f6f4 with unit E8M0 scales (the rows' fp32
-// scales are applied to the accumulator in the epilogue, as gemm_f32.hip's
+// scales are applied to the accumulator in the epilogue, as gemm_lp.hip's
 // fp8 tiles do), two 64-deep k-steps per k-tile: 4 MFMAs per phase, each
 // twice the cycles of the bf16 32x32x16 at 4x the k, so the phase is as long
 // as the bf16 phase over the same LDS bytes.  Lane half h holds the 32 bytes
-// of 16-B slots 4 step + 2h, +1 (gemm_f32.hip's fp8 reads); A and B use the
+// of 16-B slots 4 step + 2h, +1 (gemm_lp.hip's fp8 reads); A and B use the
 // same lane -> k map, so each dot product covers every k once.  (The
 // 16x16x128 form of this tile left the compiler copying its accumulators and
 // spilling, 68-128 B per lane, which broke the counted waits.)
-#include "gemm_epilogue.hpp"
-#include "rr_internal.hpp"
+#include "gemm_tile.hpp"
 
 namespace rr {
 
 namespace {
 
 constexpr int P8_HALF = 128 * 128;  // bytes per half-tile (128 rows x 128 B)
-
-__device__ __forceinline__ int swz8(int row, int slot) { return slot ^ ((row >> 1) & 7); }
 
 template <int EM, int DT>
 __global__ __launch_bounds__(512, 1) void gemm_8p_kernel(GemmArgs g, int tiles_n) {
@@ -67,7 +64,7 @@ __global__ __launch_bounds__(512, 1) void gemm_8p_kernel(GemmArgs g, int tiles_n
   const int nk = g.K / EPR;  // even (K % (2 EPR) == 0, checked on the host)
 
   // LDS-DMA sources: instruction i of wave w fills rows (i*8 + w)*8 .. +7 of a
-  // half, lane l -> row + l/8, physical slot l%8 (logical slot swz8 of it)
+  // half, lane l -> row + l/8, physical slot l%8 (logical slot swz of it)
   const unsigned char* src[4][2];
 #pragma unroll
   for (int h = 0; h < 4; ++h)
@@ -78,7 +75,7 @@ __global__ __launch_bounds__(512, 1) void gemm_8p_kernel(GemmArgs g, int tiles_n
       const int row = (isa ? m0 : n0) + (h & 1) * 128 + r;
       const int lim = (isa ? g.M : g.N) - 1;
       const unsigned char* base = reinterpret_cast<const unsigned char*>(isa ? g.A : g.B);
-      src[h][i] = base + ((long long)min(row, lim) * (isa ? g.lda : g.ldb)) * (F8 ? 1 : 2) + swz8(r, lane & 7) * 16;
+      src[h][i] = base + ((long long)min(row, lim) * (isa ? g.lda : g.ldb)) * (F8 ? 1 : 2) + swz(r, lane & 7) * 16;
     }
   auto stage = [&](int h, int kt, int buf) {
     const int t = min(kt, nk - 1);
@@ -109,8 +106,8 @@ __global__ __launch_bounds__(512, 1) void gemm_8p_kernel(GemmArgs g, int tiles_n
   // fb[st] = the 32 bytes of k-step st of row l32 of 32-row tile i
   i32x8 fa[4], fb[2];
   auto rd32 = [&](const unsigned char* base, int row, int s0, int s1) {
-    const i32x4 x = *reinterpret_cast<const i32x4*>(base + row * 128 + swz8(row, s0) * 16);
-    const i32x4 y = *reinterpret_cast<const i32x4*>(base + row * 128 + swz8(row, s1) * 16);
+    const i32x4 x = *reinterpret_cast<const i32x4*>(base + row * 128 + swz(row, s0) * 16);
+    const i32x4 y = *reinterpret_cast<const i32x4*>(base + row * 128 + swz(row, s1) * 16);
     return __builtin_shufflevector(x, y, 0, 1, 2, 3, 4, 5, 6, 7);
   };
 
@@ -239,7 +236,7 @@ __global__ __launch_bounds__(512, 1) void gemm_8p_kernel(GemmArgs g, int tiles_n
   constexpr int QA[4] = {0, 0, 1, 1}, QB[4] = {0, 1, 1, 0};
   if constexpr (F8) {
     // acc8[q][i][r]: row = qa*128 + wr*64 + 32 i + (r & 3) + 8 (r >> 2) + 4 lh,
-    // col = qb*128 + wc*32 + l32; the rows' fp32 scales first (gemm_f32.hip's
+    // col = qb*128 + wc*32 + l32; the rows' fp32 scales first (gemm_lp.hip's
     // fp8 order: acc * s_a * s_b), one quadrant at a time (all at once spilled)
     const bool scaled = g.scale_a != nullptr || g.scale_b != nullptr;
 #pragma unroll
@@ -277,15 +274,7 @@ __global__ __launch_bounds__(512, 1) void gemm_8p_kernel(GemmArgs g, int tiles_n
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
               const int mb = m0 + QA[q] * 128 + wr * 64 + 32 * i + 8 * b + 4 * lh;
-              float* dst = g.C + (long long)n * g.ldc + mb;
-              if (mb + 3 < g.M) {
-                *reinterpret_cast<f32x4*>(dst) =
-                    f32x4{acc8[q][i][4 * b], acc8[q][i][4 * b + 1], acc8[q][i][4 * b + 2], acc8[q][i][4 * b + 3]};
-              } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                  if (mb + e < g.M) dst[e] = acc8[q][i][4 * b + e];
-              }
+              store_rows4(g, true, acc8[q][i], 4 * b, n, mb);
             }
         }
       }
@@ -323,14 +312,7 @@ __global__ __launch_bounds__(512, 1) void gemm_8p_kernel(GemmArgs g, int tiles_n
 #pragma unroll
         for (int mg = 0; mg < 4; ++mg) {
           const int mb = m0 + QA[q] * 128 + wr * 64 + mg * 16 + 4 * lg;
-          float* dst = g.C + (long long)n * g.ldc + mb;
-          if (mb + 3 < g.M) {
-            *reinterpret_cast<f32x4*>(dst) = acc[q][mg][ng];
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (mb + e < g.M) dst[e] = acc[q][mg][ng][e];
-          }
+          store_rows4(g, true, acc[q][mg][ng], 0, n, mb);
         }
       }
   }
@@ -362,7 +344,7 @@ hipError_t launch_gemm_8p(const GemmArgs& g, int emode, hipStream_t s, int dt) {
   else if (emode == E_SCORES_T)
     hipLaunchKernelGGL((gemm_8p_kernel<E_SCORES_T, DT_BF16>), dim3((unsigned)nblk), dim3(512), 0, s, g, (int)tiles_n);
   else
-    return hipErrorInvalidValue;  // stored C: the 256x256 tile of gemm_f32.hip (config 3)
+    return hipErrorInvalidValue;  // stored C: the 256x256 tile of gemm_lp.hip (config 3)
   return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // gemm_epilogue.hpp — the stored-C epilogue shared by the GEMM kernels
-// (gemm_f32.hip, h2_*.hip): bias, residual, ReLU / QuickGELU, fp32 or
+// (gemm_f32.hip, gemm_lp.hip, gemm_lpp.hip, h2_*.hip): bias, residual, ReLU / QuickGELU, fp32 or
 // bf16 output, written as whole rows through an LDS-staged tile.
 #pragma once
 

@@ -2,7 +2,7 @@
 // networks/model.py:171-192: in-proj / out-proj / c_fc / c_proj) as a
 // persistent 256x256 k-stream.
 //
-// The one-tile-per-block 256x256 bf16 tile (gemm_f32.hip, lp config 3) runs
+// The one-tile-per-block 256x256 bf16 tile (gemm_lp.hip, lp config 3) runs
 // every tile as prologue (first k-tile's DMA round trip) -> 12 k-tiles at K =
 // 768 -> epilogue (bias, GELU / residual, the LayerNorm partials and bf16
 // copy, the fold's per-row correction; up to 640 KB of HBM traffic per tile)
@@ -30,15 +30,11 @@
 
 #include <algorithm>
 
-#include "gemm_epilogue.hpp"
-#include "rr_internal.hpp"
+#include "gemm_tile.hpp"
 
 namespace rr {
 
 namespace {
-
-// the 16-B slot swizzle of a 128-B LDS row (as gemm_f32.hip swz<32>)
-__device__ __forceinline__ int lswz(int row, int slot) { return slot ^ ((row >> 1) & 7); }
 
 __device__ __forceinline__ int lpp_opaque(int v) {
   asm volatile("" : "+v"(v));
@@ -95,14 +91,14 @@ __global__ __launch_bounds__(512, 1) void gemm_lpp_kernel(GemmArgs g, int tiles_
       const int row = cr + i * RPP;
       const int m = min(m0 + row, g.M - 1);
       __builtin_amdgcn_global_load_lds(
-          (const void*)(Ab + (long long)m * g.lda + kt * EPR + lswz(row, sl) * 8),
+          (const void*)(Ab + (long long)m * g.lda + kt * EPR + swz(row, sl) * 8),
           (__attribute__((address_space(3))) void*)(la + (i * RPP + wave * (64 / SLOTS)) * BK), 16, 0, 0);
     }
 #pragma unroll
     for (int i = 0; i < B_CH; ++i) {
       const int row = cr + i * RPP;
       __builtin_amdgcn_global_load_lds(
-          (const void*)(Bb + (long long)(n0 + row) * g.ldb + kt * EPR + lswz(row, sl) * 8),
+          (const void*)(Bb + (long long)(n0 + row) * g.ldb + kt * EPR + swz(row, sl) * 8),
           (__attribute__((address_space(3))) void*)(lb + (i * RPP + wave * (64 / SLOTS)) * BK), 16, 0, 0);
     }
   };
@@ -132,14 +128,14 @@ __global__ __launch_bounds__(512, 1) void gemm_lpp_kernel(GemmArgs g, int tiles_
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int row = wm * WTM + i * 32 + h * 16 + l16;
-          af[st][i][h] = *reinterpret_cast<const bf16x8*>(la + row * BK + lswz(row, 4 * st + lg) * 4);
+          af[st][i][h] = *reinterpret_cast<const bf16x8*>(la + row * BK + swz(row, 4 * st + lg) * 4);
         }
 #pragma unroll
       for (int j = 0; j < FN; ++j)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int row = wn * WTN + j * 32 + h * 16 + l16;
-          bf[st][j][h] = *reinterpret_cast<const bf16x8*>(lb + row * BK + lswz(row, 4 * st + lg) * 4);
+          bf[st][j][h] = *reinterpret_cast<const bf16x8*>(lb + row * BK + swz(row, 4 * st + lg) * 4);
         }
     };
     rd(0);
@@ -155,15 +151,7 @@ __global__ __launch_bounds__(512, 1) void gemm_lpp_kernel(GemmArgs g, int tiles_
           for (int t = 0; t < 4; ++t)
             acc4[i][j][t] =
                 __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[st][i][t >> 1], bf[st][j][t & 1], acc4[i][j][t], 0, 0, 0);
-      if (st + 1 < BK / 16) {
-        // MFMA, read, MFMA, read, ... then the remaining MFMAs
-#pragma unroll
-        for (int x = 0; x < 2 * (FM + FN); ++x) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, 4 * FM * FN - 2 * (FM + FN), 0);
-      }
+      if (st + 1 < BK / 16) interleave<2 * (FM + FN), 4 * FM * FN>();
     }
     __builtin_amdgcn_s_setprio(0);
   };
@@ -339,7 +327,7 @@ __global__ __launch_bounds__(512, 1) void gemm_lpp3_kernel(GemmArgs g, int tiles
 #pragma unroll
     for (int i = 0; i < A_CH; ++i) {
       const int row = cr + i * RPP, m = min(m0 + row, g.M - 1);
-      __builtin_amdgcn_global_load_lds((const void*)(Ab + (long long)m * g.lda + kt * EPR + lswz(row, sl) * 8),
+      __builtin_amdgcn_global_load_lds((const void*)(Ab + (long long)m * g.lda + kt * EPR + swz(row, sl) * 8),
                                        (__attribute__((address_space(3))) void*)(sa(buf) + (i * RPP + wave * 8) * BK),
                                        16, 0, 0);
     }
@@ -351,7 +339,7 @@ __global__ __launch_bounds__(512, 1) void gemm_lpp3_kernel(GemmArgs g, int tiles
 #pragma unroll
     for (int i = 0; i < B_CH; ++i) {
       const int row = cr + i * RPP;
-      __builtin_amdgcn_global_load_lds((const void*)(Bb + (long long)(n0 + row) * g.ldb + kt * EPR + lswz(row, sl) * 8),
+      __builtin_amdgcn_global_load_lds((const void*)(Bb + (long long)(n0 + row) * g.ldb + kt * EPR + swz(row, sl) * 8),
                                        (__attribute__((address_space(3))) void*)(sb(buf) + (i * RPP + wave * 8) * BK),
                                        16, 0, 0);
     }
@@ -374,14 +362,14 @@ __global__ __launch_bounds__(512, 1) void gemm_lpp3_kernel(GemmArgs g, int tiles
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int row = wm * WTM + i * 32 + h * 16 + l16;
-          af[st][i][h] = *reinterpret_cast<const bf16x8*>(la + row * BK + lswz(row, 4 * st + lg) * 4);
+          af[st][i][h] = *reinterpret_cast<const bf16x8*>(la + row * BK + swz(row, 4 * st + lg) * 4);
         }
 #pragma unroll
       for (int j = 0; j < FN; ++j)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int row = wn * WTN + j * 32 + h * 16 + l16;
-          bf[st][j][h] = *reinterpret_cast<const bf16x8*>(lb + row * BK + lswz(row, 4 * st + lg) * 4);
+          bf[st][j][h] = *reinterpret_cast<const bf16x8*>(lb + row * BK + swz(row, 4 * st + lg) * 4);
         }
     };
     rd(0);
@@ -397,14 +385,7 @@ __global__ __launch_bounds__(512, 1) void gemm_lpp3_kernel(GemmArgs g, int tiles
           for (int t = 0; t < 4; ++t)
             acc4[i][j][t] =
                 __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[st][i][t >> 1], bf[st][j][t & 1], acc4[i][j][t], 0, 0, 0);
-      if (st + 1 < BK / 16) {
-#pragma unroll
-        for (int x = 0; x < 2 * (FM + FN); ++x) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, 4 * FM * FN - 2 * (FM + FN), 0);
-      }
+      if (st + 1 < BK / 16) interleave<2 * (FM + FN), 4 * FM * FN>();
     }
     __builtin_amdgcn_s_setprio(0);
   };
@@ -546,7 +527,7 @@ static hipError_t launch_lpp_t(GemmArgs g, hipStream_t s, int n_cu) {
 
 }  // namespace
 
-// The ViT linears' epilogue flag sets (as gemm_f32.hip launch_t); other flag
+// The ViT linears' epilogue flag sets (as gemm_lp.hip launch_t); other flag
 // sets return hipErrorNotSupported (the caller runs the one-tile kernel).
 bool lpp_eligible(const GemmArgs& g) {
   // (K <= 1024: c_proj, K = 3072, ran 11 % slower than the one-tile kernel)

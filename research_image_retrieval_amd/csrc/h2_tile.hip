@@ -33,7 +33,7 @@ namespace rr {
 // IL (the 32x32x16 two-stage loop, dense or Cin % 32 == 0 conv A): the next
 // k-tiles' B DMA and A loads are not issued as one burst at the top of the
 // k-tile but one instruction group at a time among the first MFMAs of its
-// first k-step (see gemm_f32.hip IL: a burst of every wave's loads at once
+// first k-step (see gemm_lp.hip IL: a burst of every wave's loads at once
 // fills the vector-memory issue queue and stalls the MFMAs behind it).
 template <int WM, int WN, int FM, int FN, int BK, int AMODE, int MINB, int MF16, int EPI, int NSTG = 2, int POOL = 0,
           int ACC1 = 0, int IL = 0>

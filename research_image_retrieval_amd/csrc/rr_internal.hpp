@@ -28,7 +28,7 @@ struct rr_handle_s {
     int halo_mf = -1;      // f16x2 halo 3x3 tiles on v_mfma_f32_16x16x32_f16 (1) or 32x32x16 (0); -1: the pick (the 256x256 tile 1, the others 0)
     int halo_2d = -1;      // the 2-D block halo tiles: -1 where no raster halo holds the map, 1 wherever one serves, 0 never
     int s3_cfg_res = 0;    // split cores: forced tile config for the GEMMs with a residual epilogue only (0: s3_cfg's)
-    int sweep_form = -1;   // bf16 filter sweeps: 0 = gemm_f32.hip's tiles, 1 / 2 = sweep16.hip on 128-B / 64-B LDS rows; -1: the pick
+    int sweep_form = -1;   // bf16 filter sweeps: 0 = gemm_lp.hip's tiles, 1 / 2 = sweep16.hip on 128-B / 64-B LDS rows; -1: the pick
   } tune;
   int n_cu = 0;  // compute units of the handle's device (device_cu_count)
   // timing (see rr_timing_enable)
@@ -131,7 +131,7 @@ __host__ __device__ inline float key_score(unsigned long long k) {
   return unord_f32((uint32_t)(k >> 32));
 }
 
-// ---- GEMM core launchers (gemm_f32.hip) ---------------------------------
+// ---- GEMM core launchers (gemm_f32.hip, gemm_lp.hip) --------------------
 // Rows of the threshold-seeding sample of the cosine top-k rankers (exact
 // for any sample >= k rows).  About 2 % of the shard, capped at 32768 and
 // floored at 4096: on a row-sharded gallery the seed GEMM + select cost per
@@ -238,7 +238,7 @@ struct GemmArgs {
   const float* colsum = nullptr;
   int stats_k = 0;
   float ln_eps = 0.f;
-  // the 256x320 bf16 filter sweep's 16x16x32 MFMA form (gemm_kernel MF16 = 2)
+  // the 256x320 bf16 filter sweep's 16x16x32 MFMA form (gemm_lp_kernel MF16 = 2)
   int mf16_sweep = 0;
   int issue_spread = 0;
   int halo_mf = -1;
@@ -277,6 +277,9 @@ __device__ __forceinline__ void tile_coords(int bid, int nwg, int tiles_n, int& 
 
 int launch_gemm(rr_handle_s* h, int amode, int emode, const GemmArgs& a, hipStream_t s, int timer_cls,
                 int dt = DT_F32);
+// the bf16 / fp8 half of launch_gemm (gemm_lp.hip; dense A): its checks and
+// the choice among the one-tile kernels, gemm_lpp.hip, gemm_8p.hip and sweep16.hip
+int launch_gemm_lp(rr_handle_s* h, int emode, const GemmArgs& g, hipStream_t s, int timer_cls, int dt);
 
 // fp32-accurate GEMM on the 16-bit matrix cores (the f16x2 split core,
 // h2_dispatch.hip): A fp32 (A_DENSE, A_CONV or A_CONV_C4), E_STORE epilogue;

@@ -2,7 +2,7 @@
 // similarity GEMM; pass 2 of rr_cosine_topk_prefilter and the bf16
 // rr_cosine_topk_lp) on v_mfma_f32_16x16x32_bf16 with a hand-placed k-loop.
 //
-// Why a separate kernel.  The 256x320 filter tile of gemm_f32.hip leaves its
+// Why a separate kernel.  The 256x320 filter tile of gemm_lp.hip leaves its
 // k-loop schedule to hipcc, which waits lgkmcnt(0) right after issuing the
 // next k-step's fragment reads (their latency is exposed once per 10 MFMAs)
 // and runs on v_mfma_f32_32x32x16_bf16, whose 16x16x32 form holds a higher
@@ -26,7 +26,7 @@
 //     every ds_read_b128 lane group of the 16-row fragment read covers the 64
 //     banks once (MI355X_MICROARCH.md §LDS, ds_read_b128 lane groups).  The
 //     DMA writes rows linearly; the swizzle is applied to its source slot.
-// The filter epilogue is gemm_f32.hip's: every score s' > tau[query] (as
+// The filter epilogue is gemm_lp.hip's: every score s' > tau[query] (as
 // !(s' <= tau)) is appended as a 64-bit key with one atomic per survivor.
 // The bf16 products are exact in fp32 and the accumulation order is covered
 // by the prefilter's bound (prefilter.hip), so the exact ranker's output does
@@ -534,8 +534,8 @@ __global__ __launch_bounds__(512, 1) void sweep128_kernel(GemmArgs g, int tiles_
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
 
   // fragment reads: row r0 + (lane & 15), logical slot 4 s + (lane >> 4) at
-  // physical slot (4 s + (lane >> 4)) ^ ((row >> 1) & 7) (gemm_f32.hip's
-  // 128-B-row swizzle: conflict-free for this read)
+  // physical slot (4 s + (lane >> 4)) ^ ((row >> 1) & 7) (gemm_tile.hpp's
+  // 128-B-row swizzle swz: conflict-free for this read)
   const int lr = lane & 15, lg = lane >> 4, sw = (lr >> 1) & 7;
   const uint32_t lp0 = (uint32_t)(lr * 128 + ((lg ^ sw) << 4));
   const uint32_t lp1 = (uint32_t)(lr * 128 + (((4 + lg) ^ sw) << 4));

@@ -3,7 +3,7 @@
 // class/positional token assembly (:226-227) and a fused multi-head
 // attention (nn.MultiheadAttention inside ResidualAttentionBlock, :171-188).
 // The projections (QKV, out-proj, MLP with QuickGELU, ln_post @ proj) run on
-// the fp32 MFMA GEMM core (gemm_f32.hip).
+// the GEMM cores (gemm_f32.hip; bf16: gemm_lp.hip, gemm_lpp.hip).
 #include "rr_internal.hpp"
 
 namespace rr {

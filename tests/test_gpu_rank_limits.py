@@ -266,28 +266,49 @@ def _nan_case(nq, d):
     return q, g, g40, expect, s100
 
 
+def _assert_nan_expectation(s, i, order, ref_s, kk):
+    """(s, i) of an exact ranker against the oracle's stable order and scores
+    (first kk columns; the rest padding): NaN scores last, by index; the NaN
+    query returns 0..kk-1."""
+    s, i = s.cpu().numpy(), i.cpu().numpy()
+    assert np.array_equal(i[:, :kk], order[:, :kk]), np.argwhere(i[:, :kk] != order[:, :kk])[:5]
+    assert np.array_equal(np.isnan(s[:, :kk]), np.isnan(ref_s))
+    fin = ~np.isnan(ref_s)
+    assert np.array_equal(s[:, :kk][fin], ref_s[fin])
+    assert (i[:, kk:] == -1).all() and np.isneginf(s[:, kk:]).all()
+    assert list(i[NAN_Q, :kk]) == list(range(kk)) and np.isnan(s[NAN_Q, :kk]).all()
+
+
 @pytest.mark.parametrize("nq,d,tune", [
     (6, 128, dict(sweep_form=0)), (6, 128, dict(sweep_form=1)), (6, 128, dict(sweep_form=2)),
     (256, 256, dict(sweep_form=0)), (256, 256, dict(sweep_form=1)), (256, 256, dict(sweep_form=2)),
     (256, 256, dict(sweep_form=0, lp_cfg=3)), (256, 256, dict(sweep_form=0, lp_cfg=4)),
     (256, 256, dict(sweep_form=0, lp_cfg=5)),
+    (33, 192, dict(sweep_form=0, lp_cfg=2)), (33, 192, dict(sweep_form=0, lp_cfg=4, sweep_il=0)),
+    (33, 192, dict(sweep_form=0, lp_cfg=4, sweep_mf16=1, sweep_il=0)),
+    (33, 192, dict(sweep_form=0, lp_cfg=4, sweep_mf16=1)),
 ], ids=lambda v: "-".join(f"{a}{b}" for a, b in v.items()) if isinstance(v, dict) else str(v))
 def test_nan_rank_last_prefilter_every_sweep(cuda, nq, d, tune):
     """The expectation of test_nan_rows_and_queries_rank_last (NaN scores rank
     after every number, by index; the NaN query returns 0..k-1; k > #rows pads
     with (-inf, -1)) for the exact prefilter ranker under every bf16 filter
     sweep.  Which kernel runs pass 2 (and, for the gemm core's configs, the
-    seed scores) is read off launch_lp / launch_lp_cfg in csrc/gemm_f32.hip:
+    seed scores) is read off launch_lp / launch_lp_cfg in csrc/gemm_lp.hip:
 
     * sweep_form 0 at the default lp_cfg: pick_lp's cost model gives the
-      128x128 tile of gemm_kernel (16x16x32 bf16 MFMA) at both (6, 128) and
+      128x128 tile of gemm_lp_kernel (16x16x32 bf16 MFMA) at both (6, 128) and
       (256, 256) over 20000 rows;
     * sweep_form 1: sweep128_kernel of csrc/sweep16.hip (128-B LDS rows, K %
       64 == 0: both d qualify); sweep_form 2: sweep16_kernel<8> (64-B rows);
       nq = 256 leaves 64 of the tile's 320 query columns as padding, whose
       threshold is +inf;
-    * lp_cfg 3: gemm_kernel's 8-wave 256x256 tile (LDS-DMA, K % 64 == 0);
-      lp_cfg 4: its 256x320 tile on 32x32x16 MFMA (launch_t1<4, 2, 2, 5>);
+    * lp_cfg 3: gemm_lp_kernel's 8-wave 256x256 tile (LDS-DMA, K % 64 == 0);
+      lp_cfg 4: its 256x320 tile on 32x32x16 MFMA (launch_t1<4, 2, 2, 5>),
+      by default with the next k-tile's DMA spread among the MFMAs; sweep_il 0:
+      as one burst; sweep_mf16 1: the tile's 16x16x32 form, with either DMA
+      issue; lp_cfg 2: the 4-wave 256x64 tile.  These four run 33 queries
+      (a ragged query tile) at d = 192 (three whole 64-deep k-tiles: both LDS
+      buffers, an odd tile count);
     * lp_cfg 5: the 8-phase pipeline of csrc/gemm_8p.hip (K % 128 == 0), its
       E_FILTER and, for the seed, E_SCORES_T epilogues; 256 queries = one
       full panel.
@@ -297,14 +318,23 @@ def test_nan_rank_last_prefilter_every_sweep(cuda, nq, d, tune):
         qd, gd = _dev(cuda, q, gal)
         with ops.tuning(cuda.index, **tune):
             s, i = _prefilter(qd, gd, k)
-        s, i = s.cpu().numpy(), i.cpu().numpy()
-        kk = min(k, gal.shape[0])
-        assert np.array_equal(i[:, :kk], order[:, :kk]), np.argwhere(i[:, :kk] != order[:, :kk])[:5]
-        assert np.array_equal(np.isnan(s[:, :kk]), np.isnan(ref_s))
-        fin = ~np.isnan(ref_s)
-        assert np.array_equal(s[:, :kk][fin], ref_s[fin])
-        assert (i[:, kk:] == -1).all() and np.isneginf(s[:, kk:]).all()
-        assert list(i[NAN_Q, :kk]) == list(range(kk)) and np.isnan(s[NAN_Q, :kk]).all()
+        _assert_nan_expectation(s, i, order, ref_s, min(k, gal.shape[0]))
+
+
+@pytest.mark.parametrize("cfg,bk", [(22, 16), (22, 32), (41, 16), (41, 32)])
+def test_nan_rank_last_exact_every_f32_tile(cuda, cfg, bk):
+    """The same expectation for rr_cosine_topk on each tile of the fp32 core
+    (gemm_f32_kernel, csrc/gemm_f32.hip) that serves the rankers: 128x128
+    (gemm_cfg 22) and 256x64 (41) at k-tile depth 16 and 32, their E_SCORES_T
+    (the seed sample) and E_FILTER (the rows past it) epilogues.  The default
+    pick only reaches 22 / 16 at these sizes.  33 queries at d = 192: a ragged
+    query tile, 12 or 6 k-tiles."""
+    q, g, g40, expect, _ = _nan_case(33, 192)
+    for (gal, k), (order, ref_s) in zip(((g, 100), (g40, 60)), expect):
+        qd, gd = _dev(cuda, q, gal)
+        with ops.tuning(cuda.index, gemm_cfg=cfg, gemm_bk=bk):
+            s, i = ops.cosine_topk(qd, gd, k)
+        _assert_nan_expectation(s, i, order, ref_s, min(k, gal.shape[0]))
 
 
 @pytest.mark.parametrize("dtype,nq,d,tune", [
@@ -313,17 +343,18 @@ def test_nan_rank_last_prefilter_every_sweep(cuda, nq, d, tune):
     ("bf16", 256, 256, dict(sweep_form=1)), ("bf16", 256, 256, dict(sweep_form=2)),
     ("bf16", 256, 256, dict(sweep_form=0, lp_cfg=5)),
     ("fp8", 6, 128, dict(lp_cfg=0)), ("fp8", 256, 256, dict(lp_cfg=0)), ("fp8", 256, 256, dict(lp_cfg=3)),
-    ("fp8", 256, 256, dict(lp_cfg=5)),
+    ("fp8", 256, 256, dict(lp_cfg=5)), ("fp8", 33, 384, dict(lp_cfg=2)),
 ], ids=lambda v: "-".join(f"{a}{b}" for a, b in v.items()) if isinstance(v, dict) else str(v))
 def test_nan_rank_last_lowp_every_sweep(cuda, dtype, nq, d, tune):
     """NaN rows and a NaN query through rr_cosine_topk_lp.  Kernels (launch_lp
-    in csrc/gemm_f32.hip): bf16 takes the same sweeps as the prefilter's pass 2
-    (sweep_form 0 + lp_cfg 0: gemm_kernel's 128x128 tile; sweep_form 1 / 2:
+    in csrc/gemm_lp.hip): bf16 takes the same sweeps as the prefilter's pass 2
+    (sweep_form 0 + lp_cfg 0: gemm_lp_kernel's 128x128 tile; sweep_form 1 / 2:
     sweep128_kernel / sweep16_kernel<8> of csrc/sweep16.hip; lp_cfg 5: the
     8-phase bf16 pipeline of csrc/gemm_8p.hip, K % 128 == 0).  fp8 has no
-    sweep16 form (it carries row scales): lp_cfg 0 is gemm_kernel's 128x128
-    tile dequantising in its epilogue, lp_cfg 3 its 8-wave 256x256 tile on the
-    block-scaled MFMA, lp_cfg 5 gemm_8p.hip's fp8 pipeline on the 32x32x64
+    sweep16 form (it carries row scales): lp_cfg 0 is gemm_lp_kernel's 128x128
+    tile dequantising in its epilogue, lp_cfg 2 its 256x64 tile (33 queries,
+    d = 384: a ragged query tile, three whole 128-deep k-tiles), lp_cfg 3 its
+    8-wave 256x256 tile on the block-scaled MFMA, lp_cfg 5 gemm_8p.hip's fp8 pipeline on the 32x32x64
     block-scaled MFMA (K % 256 == 0, hence d = 256) with its own scale and
     filter epilogue.
 

@@ -26,5 +26,7 @@ def test_no_kernel_uses_scratch():
     assert r.returncode == 0, "kernels using scratch:\n" + "\n".join(bad) + "\n" + r.stderr[-500:]
     # the f16x2 split-core kernels are all there (tiled, persistent, halo, stem, and the two helpers)
     for name in ("gemm_s3p_kernel<", "gemm_s3_kernel<", "gemm_s3q_kernel<", "gemm_h2_halo_kernel<",
-                 "stem_pool_halo_kernel<", "split2h_kernel", "amax_kernel"):
+                 "stem_pool_halo_kernel<", "split2h_kernel", "amax_kernel",
+                 # the fp32 and the bf16 / fp8 one-tile GEMM cores
+                 "gemm_f32_kernel<", "gemm_lp_kernel<"):
         assert name in r.stdout, name

@@ -1,7 +1,7 @@
 // fetch_ceiling.hip — how fast can every CU fill its LDS with the operands of
 // the C3 cosine sweep, and what does the sweep's MFMA work leave of that?
 //
-// The bf16 filter sweep (gemm_f32.hip, lp_cfg 4: 256 gallery rows x 320
+// The bf16 filter sweep (gemm_lp.hip, lp_cfg 4: 256 gallery rows x 320
 // queries per block, 8 waves, 1 block per CU, two 73.7 KB LDS stages, one
 // 64-deep k-tile = 576 rows x 128 B per stage) is re-created here without its
 // filter epilogue, with each part switchable:

@@ -19,8 +19,8 @@ def short(name):
 
 
 def cls_of(name):
-    """Kernel class as bench.py's timer classes: gemm_kernel<WM, WN, FM, FN,
-    AMODE, EMODE, ...> by its epilogue (EMODE 2 = cosine filter sweep, 1 =
+    """Kernel class as bench.py's timer classes: gemm_f32_kernel<WM, WN, FM, FN,
+    AMODE, EMODE, ...> and gemm_lp_kernel<WM, WN, FM, FN, EMODE, ...> by their epilogue (EMODE 2 = cosine filter sweep, 1 =
     seed scores, 0 = stored C: convs / linears); gemm_s3_kernel and the
     persistent gemm_s3p_kernel / gemm_s3q_kernel, the halo-staged gemm_h2_halo_kernel /
     stem_pool_halo_kernel = convs; sweep128 / sweep16 = cosine filter."""
@@ -34,10 +34,10 @@ def cls_of(name):
     m = re.search(r"gemm_8p_kernel<(\d)>", name)
     if m:  # the 8-phase bf16 sweep (filter / seed scores only)
         return {2: "cosine_filter", 1: "cosine_seed"}.get(int(m.group(1)), "other")
-    m = re.search(r"gemm_kernel<([^>]*)>", name)
+    m = re.search(r"gemm_(f32|lp)_kernel<([^>]*)>", name)
     if m:
-        args = [int(x) for x in m.group(1).split(",")]
-        return {2: "cosine_filter", 1: "cosine_seed"}.get(args[5], "conv_gemm")
+        args = [int(x) for x in m.group(2).split(",")]
+        return {2: "cosine_filter", 1: "cosine_seed"}.get(args[5 if m.group(1) == "f32" else 4], "conv_gemm")
     if re.search(r"select_|merge_kernel|prefilter_", name):
         return "select"
     if "attention_kernel" in name:
