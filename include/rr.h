@@ -65,7 +65,10 @@ typedef struct rr_handle_s* rr_handle_t;
  * rr_linear_s3 / rr_split3_bf16 (superseded by the f16x2 core in round 3);
  * the tuning keys RR_TUNE_SWEEP_FORM (14) and RR_TUNE_HALO_2D (15) were
  * added (round 6); 7 = entries ADDED: rr_dolg_local_pool and
- * rr_dolg_orth_fuse (the DOLG head; no existing entry changed).
+ * rr_dolg_orth_fuse (the DOLG head; no existing entry changed);
+ * rr_soa_attention (SOLAR's second-order attention block) was ADDED under 7
+ * as well: no existing entry changed, so a caller built against the earlier
+ * revision-7 header still passes the right arguments everywhere.
  * Bindings compare rr_abi_version() with the RR_ABI_VERSION they were
  * written against.                                                          */
 #define RR_ABI_VERSION 7
@@ -586,6 +589,24 @@ int rr_dolg_local_pool(rr_handle_t h, const float* y, int b, int hw, int c,
  * does.  c % 4 == 0, 16-B aligned rows.                                     */
 int rr_dolg_orth_fuse(rr_handle_t h, const float* fg, const float* m, int b,
                       int c, float* out, void* stream);
+
+/* ---- SOLAR head (networks/RetrievalNet.py:534-590) ---------------------- */
+/* The second-order attention block's core: single-head self-attention over
+ * the hw positions of a map, head width c.  fgh [b][hw][3c] fp32 NHWC is the
+ * output of ONE 1x1 conv: columns [0,c) = f and [c,2c) = g, each with its BN
+ * folded and BEFORE its ReLU (applied here on load), columns [2c,3c) = h.
+ *   out[b][i][:] = sum_j softmax_j(float(c^-0.5) * relu(f_i) . relu(g_j)) h_j
+ * out [b][hw][c].  Replaces SOABlock_GeM.forward's two bmm, the softmax and
+ * the permutes (networks/RetrievalNet.py:558-565).  Both products run on the
+ * exact-fp32 MFMA; key tiles stream past a 16-query tile with a running max
+ * and sum, so the hw x hw scores are never written anywhere.  No workspace
+ * and no float atomics: keys are visited in order, the result is the same
+ * bits on every run and for an image alone or in a batch.  A query whose
+ * relu(f) is all zero gets the plain mean of the h rows.
+ * c % 256 == 0, 256 <= c <= 1024, 1 <= hw <= 65535, fgh / out 16-B aligned
+ * (else RR_EINVAL); b == 0 is RR_OK with no launch.  Timing class 5.        */
+int rr_soa_attention(rr_handle_t h, const float* fgh, int b, int hw, int c,
+                     float* out, void* stream);
 
 #ifdef __cplusplus
 }

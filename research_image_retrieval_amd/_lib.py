@@ -73,6 +73,7 @@ SIGNATURES = {
     "rr_l2_normalize": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp]),
     "rr_dolg_local_pool": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _vp, _vp]),
     "rr_dolg_orth_fuse": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "rr_soa_attention": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "rr_linear_ex": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp]),
     "rr_layernorm": (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp, _f, _vp, _vp]),
     "rr_patchify": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

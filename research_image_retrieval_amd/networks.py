@@ -74,7 +74,7 @@ class ResNet:
         w, b = self.convs[name]
         return ops.conv2d(x, w, b, stride, pad, residual, relu)
 
-    def _forward_h2(self, x, return_x3, hook=None, return_x3_amax=False):
+    def _forward_h2(self, x, return_x3, hook=None, return_x3_amax=False, return_amax=False):
         """The trunk on the f16x2 core: every conv reads its input's max-|x|
         record and writes its output's (one zeroed [2 + 3 blocks, 64] tensor per
         forward); the max-pool output reuses the stem's record (every stem
@@ -87,7 +87,9 @@ class ResNet:
         stem) -- the point where a caller can record a stream event.
         return_x3_amax (with return_x3): also return x3's max-|x| record, which
         its conv3 published, for a caller that runs another f16x2 conv on x3:
-        (x3, x4, record)."""
+        (x3, x4, record).  return_amax: the output's own record is appended
+        to whatever is returned, (..., x4's record), for a caller that runs
+        another f16x2 conv on x4."""
         cv, h2 = self.convs, self.convs_h2
         hook = hook or (lambda i: None)
         rec = ops.amax_records(2 + 3 * sum(self.layers), x.device)
@@ -121,20 +123,27 @@ class ResNet:
             if li == 2:
                 x3, x3a = x, xa
         if return_x3 and return_x3_amax:
-            return x3, x, x3a
-        return (x3, x) if return_x3 else x
+            ret = (x3, x, x3a)
+        else:
+            ret = (x3, x) if return_x3 else (x,)
+        if return_amax:
+            return ret + (xa,)
+        return ret if return_x3 else x
 
-    def forward(self, x, return_x3=False, hook=None, return_x3_amax=False):
+    def forward(self, x, return_x3=False, hook=None, return_x3_amax=False, return_amax=False):
         """x: NHWC fp32 with 3 channels or 4 (zero 4th channel, preferred).
         return_x3: also return layer3's output, as ResNet_DOLG.forward's
         (x3, x4) (networks/backbone.py:236-242).  return_x3_amax (f16x2 trunk,
-        with return_x3): (x3, x4, x3's max-|x| record)."""
+        with return_x3): (x3, x4, x3's max-|x| record).  return_amax (f16x2
+        trunk): x4's max-|x| record comes last, (x4, record) or (x3, x4, [x3's
+        record,] record)."""
         if x.shape[-1] == 3:
             x = torch.nn.functional.pad(x, (0, 1))
         if self.conv_math == "h2":
-            return self._forward_h2(x.contiguous(), return_x3, hook, return_x3_amax)
-        if return_x3_amax:
-            raise ValueError("return_x3_amax: only the f16x2 trunk (conv_math='h2') keeps max-|x| records")
+            return self._forward_h2(x.contiguous(), return_x3, hook, return_x3_amax, return_amax)
+        if return_x3_amax or return_amax:
+            raise ValueError("return_x3_amax / return_amax: only the f16x2 trunk (conv_math='h2') keeps max-|x| "
+                             "records")
         x = self._conv(x, "conv1", 2, 3, True)
         x = ops.maxpool2d(x, 3, 2, 1)
         x3 = None
@@ -349,6 +358,99 @@ class DOLG(_Extractor):
         m = self.local_mean(x3, x3_amax)
         fg = ops.linear(self.pool_g(x4), *self.fc_t)
         f = ops.linear(ops.dolg_orth_fuse(fg, m), *self.fc)
+        return ops.l2_normalize(f, EPS_L2, out=f)
+
+
+class SOABlock_GeM:
+    """SOLAR's pooling stage (networks/RetrievalNet.py:534-569): second-order
+    attention over the map's positions, the 1x1 conv v, the residual, gem(p=3).
+    Callable on x4 NHWC [B,H,W,in_ch] -> pooled [B,in_ch].
+
+    Four launches: the f, g and h 1x1 convs as ONE conv (Cout = 3 in_ch / k,
+    BN folded, no ReLU), rr_soa_attention (applies f's and g's ReLU on load,
+    online softmax, the scores never stored), the v conv with x4 as its
+    residual epilogue, rr_gem_pool.  head: weights.solar_head_from_state_dict's
+    dict (fgh_w, fgh_b, v_w, v_b).  conv_math "h2" runs both convs on the f16x2
+    core: x4's max-|x| record is the trunk's (x4_amax; computed here when the
+    caller has none), the attention output's comes from ops.amax_f32."""
+
+    def __init__(self, in_ch, k, head, device="cuda", conv_math="h2"):
+        if conv_math not in ("h2", "f32"):
+            raise ValueError("conv_math must be 'h2' or 'f32'")
+        self.in_ch, self.out_ch, self.mid_ch = in_ch, in_ch, in_ch // k
+        if tuple(head["fgh_w"].shape) != (3 * self.mid_ch, 1, 1, in_ch) or \
+                tuple(head["v_w"].shape) != (in_ch, 1, 1, self.mid_ch):
+            raise ValueError("networks.SOABlock_GeM: head weight shapes do not fit in_ch and k")
+        self.device = torch.device(device)
+        self.conv_math = conv_math
+        self.fgh_w, self.fgh_b = head["fgh_w"].to(self.device), head["fgh_b"].to(self.device)
+        self.v_w, self.v_b = head["v_w"].to(self.device), head["v_b"].to(self.device)
+        self.fgh_h2 = ops.H2Conv(self.fgh_w) if conv_math == "h2" else None
+        self.v_h2 = ops.H2Conv(self.v_w) if conv_math == "h2" else None
+        self.pooling = gem(3.0)
+
+    def attended(self, x4, x4_amax=None):
+        """z = v(softmax(c^-0.5 f^T g) h^T) + x4, NHWC (:558-567)."""
+        if self.conv_math == "h2":
+            if x4_amax is None:
+                x4_amax = ops.amax_f32(x4, ops.amax_records(1, x4.device)[0])
+            fgh = ops.conv2d_h2(x4, x4_amax, self.fgh_h2, self.fgh_b, 1, 0, None, False)
+            a = ops.soa_attention(fgh, self.mid_ch)
+            a_amax = ops.amax_f32(a, ops.amax_records(1, a.device)[0])
+            return ops.conv2d_h2(a, a_amax, self.v_h2, self.v_b, 1, 0, x4, False)
+        fgh = ops.conv2d(x4, self.fgh_w, self.fgh_b, 1, 0, None, False)
+        return ops.conv2d(ops.soa_attention(fgh, self.mid_ch), self.v_w, self.v_b, 1, 0, x4, False)
+
+    def __call__(self, x4, x4_amax=None):
+        return self.pooling(self.attended(x4, x4_amax))
+
+
+class SOLAR(_Extractor):
+    """SOLAR (networks/RetrievalNet.py:572-590, forward_test): backbone ->
+    SOABlock_GeM(2048, k=2) -> F.normalize -> whiten (1x1 conv 2048 -> 2048,
+    +bias) -> F.normalize.
+
+    Constructor: the reference's positional order (outputdim, classifier_num,
+    s, m, backbone) first; classifier_num, s and m belong to the ArcFace
+    training head and are accepted and ignored.  Then state_dict (trunk keys
+    as networks.ResNet accepts, head keys as weights.solar_head_from_state_dict),
+    seed (synthetic weights when state_dict is None), device, conv_math and
+    stride_on as networks.DOLG.  whiten always emits 2048 values (:577), so
+    outputdim must be 2048."""
+
+    in_channels = 4
+
+    def __init__(self, outputdim=2048, classifier_num=None, s=32, m=0.15, backbone="resnet101", state_dict=None,
+                 seed=0, device="cuda", conv_math="h2", stride_on="3x3"):
+        if outputdim != 2048:
+            raise ValueError("networks.SOLAR requires outputdim == 2048 (whiten is Conv2d(2048, 2048), "
+                             "networks/RetrievalNet.py:577)")
+        self.device = torch.device(device)
+        if state_dict is None:
+            head = W.solar_head_from_state_dict(W.synthetic_solar_head(seed + 1))
+        else:
+            head = W.solar_head_from_state_dict(state_dict)
+        self.backbone = ResNet(backbone, state_dict, seed, device, conv_math, stride_on)
+        cin = self.backbone.outputdim_block5
+        if head["whiten_w"].shape != (2048, cin):
+            raise ValueError("networks.SOLAR: whiten weight shape does not fit the trunk")
+        self.conv_math = conv_math
+        self.pooling = SOABlock_GeM(cin, 2, head, device, conv_math)
+        self.whiten_w = head["whiten_w"].to(self.device)
+        self.whiten_b = head["whiten_b"].to(self.device)
+        self.outputdim = outputdim
+        self.meta = {"outputdim": outputdim}
+
+    def forward_test_nhwc(self, x_nhwc, hook=None):
+        if self.conv_math == "h2":
+            x4, x4a = self.backbone(x_nhwc, hook=hook, return_amax=True)
+        else:
+            x4, x4a = self.backbone(x_nhwc), None
+        return self.tail(self.pooling(x4, x4a))
+
+    def tail(self, pooled):
+        """:587-590: F.normalize -> whiten -> F.normalize on the pooled [B,2048]."""
+        f = ops.linear(ops.l2_normalize(pooled, EPS_L2), self.whiten_w, self.whiten_b)
         return ops.l2_normalize(f, EPS_L2, out=f)
 
 

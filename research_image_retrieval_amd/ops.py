@@ -337,6 +337,24 @@ def dolg_orth_fuse(fg, m):
     return out
 
 
+def soa_attention(fgh, c):
+    """SOLAR's second-order attention (rr_soa_attention): fgh [B,H,W,3c] (or
+    [B,HW,3c]) = one 1x1 conv's output [f | g | h], f and g pre-ReLU with their
+    BN folded -> softmax(c^-0.5 relu(f) relu(g)^T) h, shaped as fgh with c
+    channels."""
+    _f32(fgh, "soa_attention fgh")
+    c = int(c)
+    if fgh.dim() not in (3, 4) or fgh.shape[-1] != 3 * c:
+        raise ValueError(f"soa_attention: expected [B,H,W,{3 * c}] or [B,HW,{3 * c}], got {tuple(fgh.shape)}")
+    dev = _dev(fgh)
+    b = fgh.shape[0]
+    hw = fgh.numel() // (b * 3 * c) if b * c else 1
+    out = torch.empty(tuple(fgh.shape[:-1]) + (c,), dtype=torch.float32, device=fgh.device)
+    hd = _lib.handle(dev)
+    _lib.check(_lib.lib().rr_soa_attention(hd, _ptr(fgh), b, hw, c, _ptr(out), _stream(dev)), hd, "rr_soa_attention")
+    return out
+
+
 def cosine_topk_workspace_size(nq, n, d, k):
     return int(_lib.lib().rr_cosine_topk_workspace_size(int(nq), int(n), int(d), int(k)))
 

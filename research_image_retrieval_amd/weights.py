@@ -256,6 +256,79 @@ def synthetic_dolg_head(seed, c=1024, c4=2048, out_dim=512):
     return sd
 
 
+# ---- SOLAR head (networks/RetrievalNet.py:534-590) --------------------------
+SOLAR_HEAD_KEYS = tuple(f"pooling.{n}.0.{k}" for n in "fg" for k in ("weight", "bias")) + \
+    tuple(f"pooling.{n}.1.{k}" for n in "fg" for k in ("weight", "bias", "running_mean", "running_var")) + \
+    ("pooling.h.weight", "pooling.h.bias", "pooling.v.weight", "pooling.v.bias", "whiten.weight", "whiten.bias")
+
+
+def solar_head_from_state_dict(sd, eps=BN_EPS):
+    """The SOLAR head of a reference checkpoint (keys pooling.{f,g}.0.* conv,
+    pooling.{f,g}.1.* BN, pooling.h.*, pooling.v.*, whiten.*; a leading
+    ``module.`` is dropped; trunk and ``classifier.*`` keys are ignored) as
+    fp32 contiguous tensors:
+
+      fgh_w [3c,1,1,Cin] NHWC-ready, fgh_b [3c]: the f, g and h 1x1 convs as
+        one conv, rows [f | g | h]; f and g with their eval-mode BN folded in,
+        the conv's OWN bias included (b' = (b_conv - mean) * scale + beta;
+        fold_bn assumes a bias-free conv), computed in float64 and rounded
+        once; their ReLU is not part of the conv (rr_soa_attention applies it);
+      v_w [Cin,1,1,c] NHWC-ready, v_b [Cin]; whiten_w [2048,Cin], whiten_b."""
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
+    missing = [k for k in SOLAR_HEAD_KEYS if k not in sd]
+    if missing:
+        raise ValueError(f"SOLAR head: missing keys {missing}")
+    ws, bs = [], []
+    for n in "fg":
+        w = sd[f"pooling.{n}.0.weight"]
+        if w.dim() != 4 or tuple(w.shape[2:]) != (1, 1):
+            raise ValueError(f"pooling.{n}.0.weight: expected [c,Cin,1,1], got {tuple(w.shape)}")
+        g, b = sd[f"pooling.{n}.1.weight"].double(), sd[f"pooling.{n}.1.bias"].double()
+        m, v = sd[f"pooling.{n}.1.running_mean"].double(), sd[f"pooling.{n}.1.running_var"].double()
+        scale = g / torch.sqrt(v + eps)
+        ws.append((w.double() * scale[:, None, None, None]).float())
+        bs.append(((sd[f"pooling.{n}.0.bias"].double() - m) * scale + b).float())
+    wh, wv = sd["pooling.h.weight"], sd["pooling.v.weight"]
+    if tuple(wh.shape) != tuple(ws[0].shape) or tuple(ws[1].shape) != tuple(ws[0].shape) or wv.dim() != 4 or \
+            tuple(wv.shape) != (wh.shape[1], wh.shape[0], 1, 1):
+        raise ValueError("SOLAR head: pooling.{f,g,h,v} conv shapes do not fit each other")
+    ws.append(wh.float())
+    bs.append(sd["pooling.h.bias"].float())
+    ww = sd["whiten.weight"]
+    return {"fgh_w": torch.cat(ws).permute(0, 2, 3, 1).contiguous(), "fgh_b": torch.cat(bs).contiguous(),
+            "v_w": wv.float().permute(0, 2, 3, 1).contiguous(), "v_b": sd["pooling.v.bias"].float().contiguous(),
+            "whiten_w": ww.float().reshape(ww.shape[0], -1).contiguous(),
+            "whiten_b": sd["whiten.bias"].float().contiguous()}
+
+
+def synthetic_solar_head(seed, cin=2048, k=2):
+    """Seeded SOLAR head weights under the reference's keys (SOLAR_HEAD_KEYS):
+    f and g conv gains that put the logits at 10-20 on post-ReLU unit-variance
+    maps (attention row maxima 0.07-0.41 on tests/golden/solar.npz's head
+    inputs, far from uniform), non-trivial BN statistics, and a NON-ZERO v: the
+    reference initialises v to zero (:553), which would make the block a no-op.
+    The fixture generator loads them into the reference's modules; the tests
+    fold them (solar_head_from_state_dict)."""
+    rs = np.random.RandomState(seed)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
+    c = cin // k
+    sd = collections.OrderedDict()
+    for n in "fg":
+        sd[f"pooling.{n}.0.weight"] = t(rs.standard_normal((c, cin, 1, 1)) * (2.0 / np.sqrt(cin)))
+        sd[f"pooling.{n}.0.bias"] = t(rs.standard_normal(c) * 0.1)
+        sd[f"pooling.{n}.1.weight"] = t(rs.uniform(0.5, 1.5, c))
+        sd[f"pooling.{n}.1.bias"] = t(rs.standard_normal(c) * 0.1)
+        sd[f"pooling.{n}.1.running_mean"] = t(rs.standard_normal(c) * 0.1)
+        sd[f"pooling.{n}.1.running_var"] = t(rs.uniform(0.5, 1.5, c))
+    sd["pooling.h.weight"] = t(rs.standard_normal((c, cin, 1, 1)) / np.sqrt(cin))
+    sd["pooling.h.bias"] = t(rs.standard_normal(c) * 0.1)
+    sd["pooling.v.weight"] = t(rs.standard_normal((cin, c, 1, 1)) / np.sqrt(c))
+    sd["pooling.v.bias"] = t(rs.standard_normal(cin) * 0.1)
+    sd["whiten.weight"] = t(rs.uniform(-1, 1, (2048, cin, 1, 1)) / np.sqrt(cin))
+    sd["whiten.bias"] = t(rs.uniform(-1, 1, 2048) / np.sqrt(cin))
+    return sd
+
+
 def folded_resnet(sd, arch):
     """torchvision-keyed trunk -> ordered list of folded (name, w, b, stride, pad)."""
     def bn(prefix):

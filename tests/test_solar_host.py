@@ -1,0 +1,183 @@
+"""SOLAR without a GPU: the new C-ABI entry, the head-weight loader, and the
+torch restatement (tests/solar_ref.py) pinned to the reference's own
+SOLAR.forward_test / SOABlock_GeM output (tests/golden/solar.npz,
+make_golden_solar.py)."""
+import collections
+import ctypes
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from research_image_retrieval_amd import _lib
+from research_image_retrieval_amd import weights as W
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLD = os.path.join(HERE, "golden")
+sys.path.insert(0, GOLD)
+sys.path.insert(0, HERE)
+import inputs as I  # noqa: E402
+import solar_ref  # noqa: E402
+
+TAGS = ("b2_224", "b1_odd")
+HEAD_CASES = ((2, 7, 7), (1, 5, 9), (1, 17, 19))
+
+
+def _tag(b, h, w):
+    return f"head_b{b}_{h}x{w}"
+
+
+def _head_input(b, h, w):
+    return torch.from_numpy(I.feature_map(7000 + h * w, b, 2048, h, w))
+
+
+@pytest.fixture(scope="module")
+def fx():
+    return np.load(os.path.join(GOLD, "solar.npz"))
+
+
+@pytest.fixture(scope="module")
+def head(fx):
+    return W.solar_head_from_state_dict(W.synthetic_solar_head(int(fx["head_seed"])))
+
+
+@pytest.fixture(scope="module")
+def ref64(head):
+    """The float64 restatement of every group-(b) case, computed once."""
+    return {c: solar_ref.head_forward(_head_input(*c), head, torch.float64) for c in HEAD_CASES}
+
+
+def test_symbols_and_abi():
+    L = ctypes.CDLL(_lib.LIB_PATH)
+    assert hasattr(L, "rr_soa_attention") and "rr_soa_attention" in _lib.SIGNATURES
+    L = _lib.lib()
+    assert L.rr_abi_version() == 7 == _lib.ABI_VERSION
+    assert L.rr_soa_attention(None, None, 1, 1, 256, None, None) == _lib.RR_EINVAL
+
+
+def test_fixture_is_no_larger_than_the_trunk_fixture():
+    assert os.path.getsize(os.path.join(GOLD, "solar.npz")) <= os.path.getsize(os.path.join(GOLD, "resnet_dolg.npz"))
+
+
+@pytest.mark.parametrize("case", HEAD_CASES)
+def test_restatement_reproduces_head_fixture(fx, ref64, case):
+    tag = _tag(*case)
+    got = ref64[case]
+    err = np.abs(got["out"].numpy() - fx[tag + "_out"]).max()
+    ref_p = fx[tag + "_pooled"]
+    err_p = (np.abs(got["pooled"].numpy() - ref_p).max(axis=1) / np.linalg.norm(ref_p, axis=1)).max()
+    print(tag, "descriptor err", err, "pooled err / row norm", err_p)
+    assert err <= 1e-6
+    assert err_p <= 1e-6
+
+
+def test_restatement_reproduces_stored_attention(fx, ref64):
+    tag = _tag(1, 5, 9)
+    got = ref64[(1, 5, 9)]
+    att, ah = fx[tag + "_att"], fx[tag + "_ah"]
+    assert att.shape == (1, 45, 45) and ah.shape == (1, 45, 1024)
+    err_att = np.abs(got["att"].numpy() - att).max()
+    err_ah = (np.abs(got["ah"].numpy() - ah).max(axis=2) / np.linalg.norm(ah, axis=2)).max()
+    print("attention err", err_att, "att.h err / row norm", err_ah, "row maxima", att.max(axis=2).min(),
+          att.max(axis=2).max())
+    assert err_att <= 1e-6
+    assert err_ah <= 1e-6
+
+
+@pytest.mark.parametrize("tag", TAGS)
+def test_restatement_reproduces_end_to_end_fixture(fx, head, tag):
+    """Group (a), from the reference trunk's saved x4 (wiring only: the seeded
+    trunk's x4 leaves the attention close to uniform)."""
+    tr = np.load(os.path.join(GOLD, "resnet_dolg.npz"))
+    assert int(tr["weight_seed"]) == int(fx["weight_seed"])
+    assert list(tr[tag + "_case"]) == list(fx[tag + "_case"])
+    got = solar_ref.head_forward(torch.from_numpy(tr[tag + "_x4"]), head, torch.float64)
+    err = np.abs(got["out"].numpy() - fx[tag + "_out"]).max()
+    print(tag, "descriptor err", err)
+    assert err <= 1e-6
+
+
+@pytest.mark.parametrize("case", HEAD_CASES)
+def test_head_fixture_is_sensitive_to_the_attention(fx, head, case):
+    """A condition on the fixture: uniform attention, or a zeroed v, is far
+    outside the 1e-6 bar the kernels are held to."""
+    tag = _tag(*case)
+    x = _head_input(*case)
+    uni = solar_ref.head_forward(x, head, torch.float64, uniform=True)["out"].numpy()
+    nov = solar_ref.head_forward(x, head, torch.float64, zero_v=True)["out"].numpy()
+    d_uni = np.abs(uni - fx[tag + "_out"]).max()
+    d_nov = np.abs(nov - fx[tag + "_out"]).max()
+    print(tag, "uniform attention moves the descriptor by", d_uni, "; v = 0 by", d_nov)
+    assert d_uni >= 1e-4
+    assert d_nov >= 1e-3
+
+
+def _reference_keyed(seed):
+    sd = W.synthetic_solar_head(seed)
+    for n in "fg":
+        sd[f"pooling.{n}.1.num_batches_tracked"] = torch.tensor(0)
+    sd["classifier.weight"] = torch.zeros(3, 2048)           # ArcFace head: ignored
+    sd["backbone.block1.0.weight"] = torch.zeros(64, 3, 7, 7)  # trunk: ignored here
+    return sd
+
+
+@pytest.mark.parametrize("prefix", ["", "module."])
+def test_head_from_state_dict_round_trip(prefix):
+    sd = _reference_keyed(5)
+    h = W.solar_head_from_state_dict(collections.OrderedDict((prefix + k, v) for k, v in sd.items()))
+    assert h["fgh_w"].shape == (3072, 1, 1, 2048) and h["fgh_b"].shape == (3072,)
+    assert h["v_w"].shape == (2048, 1, 1, 1024) and h["v_b"].shape == (2048,)
+    assert h["whiten_w"].shape == (2048, 2048) and h["whiten_b"].shape == (2048,)
+    assert torch.equal(h["fgh_w"][2048:].reshape(1024, 2048), sd["pooling.h.weight"].reshape(1024, 2048))
+    assert torch.equal(h["fgh_b"][2048:], sd["pooling.h.bias"])
+    assert torch.equal(h["v_w"].reshape(2048, 1024), sd["pooling.v.weight"].reshape(2048, 1024))
+    assert torch.equal(h["v_b"], sd["pooling.v.bias"])
+    assert torch.equal(h["whiten_w"], sd["whiten.weight"].reshape(2048, 2048))
+    assert torch.equal(h["whiten_b"], sd["whiten.bias"])
+    assert all(v.dtype == torch.float32 and v.is_contiguous() for v in h.values())
+    assert set(W.SOLAR_HEAD_KEYS) <= set(sd) and len(W.SOLAR_HEAD_KEYS) == 18
+
+
+@pytest.mark.parametrize("which,row0", [("f", 0), ("g", 1024)])
+def test_head_fold_includes_conv_bias(which, row0):
+    """bn(conv(x)) evaluated in float64 from the unfolded weights equals the
+    folded conv to fp32 rounding of the folded weights; dropping the conv's
+    own bias (what fold_bn would do) is far outside that."""
+    sd = W.synthetic_solar_head(6)
+    h = W.solar_head_from_state_dict(sd)
+    rs = np.random.RandomState(0)
+    x = torch.from_numpy(rs.standard_normal((7, 2048)))
+    p = f"pooling.{which}."
+    w, b = sd[p + "0.weight"].double().reshape(1024, 2048), sd[p + "0.bias"].double()
+    g, beta = sd[p + "1.weight"].double(), sd[p + "1.bias"].double()
+    mu, var = sd[p + "1.running_mean"].double(), sd[p + "1.running_var"].double()
+    ref = (x @ w.t() + b - mu) / torch.sqrt(var + 1e-5) * g + beta
+    fw, fb = h["fgh_w"][row0:row0 + 1024].reshape(1024, 2048), h["fgh_b"][row0:row0 + 1024]
+    got = x @ fw.double().t() + fb.double()
+    scale = g / torch.sqrt(var + 1e-5)
+    # one fp32 rounding per folded weight (2^-24 relative) over a 2048-term dot product, and of the bias
+    bound = 2.0 ** -24 * ((x.abs() @ (w * scale[:, None]).abs().t()) + (ref.abs() + 1))
+    assert bool(((got - ref).abs() <= bound).all())
+    bias64 = (b - mu) * scale + beta
+    assert torch.equal(fb, bias64.float())
+    no_bias = (beta - mu * scale).float()
+    assert (fb - no_bias).abs().max().item() > 1e-2
+
+
+def test_head_rejects_missing_keys():
+    sd = W.synthetic_solar_head(7)
+    for k in ("pooling.v.bias", "pooling.g.1.running_var", "whiten.weight"):
+        bad = dict(sd)
+        bad.pop(k)
+        with pytest.raises(ValueError, match=k.replace(".", r"\.")):
+            W.solar_head_from_state_dict(bad)
+
+
+def test_solar_rejects_outputdim_without_gpu():
+    from research_image_retrieval_amd.networks import SOLAR
+    with pytest.raises(ValueError, match="outputdim"):
+        SOLAR(outputdim=512)
+    with pytest.raises(ValueError, match="outputdim"):
+        SOLAR(512, 1000, 32, 0.15, "resnet101")  # the reference's positional order
