@@ -68,7 +68,8 @@ typedef struct rr_handle_s* rr_handle_t;
  * rr_dolg_orth_fuse (the DOLG head; no existing entry changed);
  * rr_soa_attention (SOLAR's second-order attention block) was ADDED under 7
  * as well: no existing entry changed, so a caller built against the earlier
- * revision-7 header still passes the right arguments everywhere.
+ * revision-7 header still passes the right arguments everywhere; likewise
+ * rr_attention_hd128, rr_token_pool and rr_gelu (the Token head).
  * Bindings compare rr_abi_version() with the RR_ABI_VERSION they were
  * written against.                                                          */
 #define RR_ABI_VERSION 7
@@ -607,6 +608,51 @@ int rr_dolg_orth_fuse(rr_handle_t h, const float* fg, const float* m, int b,
  * (else RR_EINVAL); b == 0 is RR_OK with no launch.  Timing class 5.        */
 int rr_soa_attention(rr_handle_t h, const float* fgh, int b, int hw, int c,
                      float* out, void* stream);
+
+/* ---- Token head (networks/RetrievalNet.py:94-187, 263-305) -------------- */
+/* Multi-head attention at head width 128 with separate query and key counts:
+ * Attention.forward's reshape / permute / q @ k^T / softmax / attn @ v /
+ * transpose (networks/RetrievalNet.py:120-124) given the projected rows.
+ * q holds b * nq rows of ldq floats, head j in columns [128 j, 128 j + 128);
+ * k and v hold b * nk rows of ldk / ldv floats likewise; out is dense
+ * [b * nq][heads * 128].  Per image and head
+ *   out[i] = sum_j softmax_j(float(128^-0.5) * q_i . k_j) v_j.
+ * The strides let the caller stack projections in one GEMM and pass column
+ * slices (q | k | v of one [rows][3 * heads * 128] buffer, or k1 | v1 | k2 | v2).
+ * Both products run on the exact-fp32 MFMA; key tiles stream past a 16-query
+ * tile with a running max and sum.  Only out is written: no workspace, no
+ * atomics, keys visited in a fixed order, so the result is the same bits on
+ * every run, for an image alone or in a batch, for a head alone (heads = 1 on
+ * its column slice) or among others, and from dense or stacked buffers.  An
+ * all-zero query gets the plain mean of the v rows.
+ * head_dim is fixed at 128; 1 <= nq, nk <= 65535; heads >= 1; ldq, ldk, ldv
+ * >= heads * 128 and % 4 == 0; q, k, v, out 16-B aligned (else RR_EINVAL);
+ * b == 0 is RR_OK with no launch; offsets are 64-bit.  Timing class 5.      */
+int rr_attention_hd128(rr_handle_t h, const float* q, long long ldq,
+                       const float* k, long long ldk, const float* v,
+                       long long ldv, int b, int nq, int nk, int heads,
+                       float* out, void* stream);
+
+/* Object-token pooling (Token_Refine.forward, networks/RetrievalNet.py:
+ * 180-182: bmm, softmax(dim=1), bmm): x [b][hw][c], query [n_obj][c],
+ *   out [b][n_obj][c] = sum_p softmax_o(query_o . x_p) x_p,
+ * the softmax over the n_obj OBJECTS of each position (max subtracted), no
+ * scale.  x is read once.  No float atomics: where few images leave the chip
+ * short of work an image's positions are split over workgroups (a function of
+ * b and hw only) and the partial sums, kept in a per-stream buffer the library
+ * owns, are added in a fixed order: the same bits on every run, and for an
+ * image alone or in a batch wherever both choose the same split (at least 16
+ * positions per workgroup, about 1024 workgroups wanted: any hw <= 16 *
+ * ceil(1024 / b)).
+ * c % 256 == 0, 256 <= c <= 1024, 1 <= n_obj <= 8, hw >= 1, x / query / out
+ * 16-B aligned (else RR_EINVAL); b == 0 is RR_OK.  Timing class 3.          */
+int rr_token_pool(rr_handle_t h, const float* x, int b, int hw, int c,
+                  const float* query, int n_obj, float* out, void* stream);
+
+/* Exact GELU, y = 0.5 x (1 + erf(x / sqrt 2)) over n floats (F.gelu in Mlp,
+ * networks/RetrievalNet.py:67-72, 87); y may be x.  NaN stays NaN, +inf gives
+ * +inf, -inf gives -0 (the limit).  Timing class 3.                         */
+int rr_gelu(rr_handle_t h, const float* x, long long n, float* y, void* stream);
 
 #ifdef __cplusplus
 }

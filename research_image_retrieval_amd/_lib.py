@@ -74,6 +74,9 @@ SIGNATURES = {
     "rr_dolg_local_pool": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _vp, _vp]),
     "rr_dolg_orth_fuse": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "rr_soa_attention": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "rr_attention_hd128": (_i, [_vp, _vp, _ll, _vp, _ll, _vp, _ll, _i, _i, _i, _i, _vp, _vp]),
+    "rr_token_pool": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "rr_gelu": (_i, [_vp, _vp, _ll, _vp, _vp]),
     "rr_linear_ex": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp]),
     "rr_layernorm": (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp, _f, _vp, _vp]),
     "rr_patchify": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

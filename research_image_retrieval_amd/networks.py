@@ -454,6 +454,161 @@ class SOLAR(_Extractor):
         return ops.l2_normalize(f, EPS_L2, out=f)
 
 
+class Token_Refine:
+    """The Token head (networks/RetrievalNet.py:164-187, with Attention :94-126,
+    Encoder :129-142, Decoder :145-161, Mlp :75-91), eval mode.  Callable on x4
+    NHWC [B,H,W,2048] -> [B,1024] (before forward_test's F.normalize).
+
+    head: weights.token_head_from_state_dict's dict.  The constructor keeps the
+    reference's (num_heads, num_object, mid_dim, encoder_layer, decoder_layer);
+    the kernels are built for heads of 128, one encoder and two decoders.
+
+    Launches, N = H W positions, 4 = num_object tokens per image:
+      per position (1x1 convs; conv_math "h2": the f16x2 core, each conv reading
+      its input's max-|x| record and publishing its output's; "f32": rr_conv2d):
+        conv + BN                 2048 -> 1024
+        encoder q | k | v         1024 -> 3072, one GEMM
+        rr_attention_hd128        nq = nk = N, column slices of the stacked rows
+        (h2: rr_amax_f32 of the attention output)
+        proj + X                  residual in the epilogue
+        mlp(BN) + X               the BatchNorm1d folded into the weights
+        decoder k1 | v1 | k2 | v2 1024 -> 4096, one GEMM for both decoders
+      rr_token_pool               softmax over the objects, A X, one read of X
+      per token (4 rows per image; rr_linear_ex / rr_layernorm always):
+        token_norm: linear, LayerNorm
+        per decoder: LayerNorm, q linear, rr_attention_hd128 (nq = 4, nk = N),
+          proj + T; fc1, rr_gelu in place, fc2 + T; LayerNorm, q | k | v linear,
+          rr_attention_hd128 (nq = nk = 4), proj + T
+      proj + BatchNorm1d          [B,4096] -> [B,1024]
+    No torch arithmetic: torch allocates buffers and takes views."""
+
+    def __init__(self, num_heads=8, num_object=4, mid_dim=1024, encoder_layer=1, decoder_layer=2, head=None,
+                 device="cuda", conv_math="h2"):
+        if conv_math not in ("h2", "f32"):
+            raise ValueError("conv_math must be 'h2' or 'f32'")
+        if mid_dim != 128 * num_heads:
+            raise ValueError("networks.Token_Refine: mid_dim must be 128 * num_heads (rr_attention_hd128)")
+        if encoder_layer != 1 or decoder_layer != 2:
+            raise ValueError("networks.Token_Refine: one encoder layer and two decoder layers")
+        if head is None:
+            raise ValueError("networks.Token_Refine needs head=weights.token_head_from_state_dict(...)")
+        if tuple(head["query"].shape) != (num_object, mid_dim) or head["conv_w"].shape[0] != mid_dim or \
+                tuple(head["out_w"].shape) != (1024, num_object * mid_dim):
+            raise ValueError("networks.Token_Refine: head weight shapes do not fit num_object and mid_dim")
+        self.heads, self.n_obj, self.mid_dim = num_heads, num_object, mid_dim
+        self.device = torch.device(device)
+        self.conv_math = conv_math
+        self.w = {k: v.to(self.device) for k, v in head.items()}
+        self.h2 = {}
+        if conv_math == "h2":
+            self.h2 = {k: ops.H2Conv(self.w[k + "_w"]) for k in ("conv", "enc_qkv", "enc_proj", "enc_mlp", "dec_kv")}
+
+    def _conv(self, x, xa, name, residual=None, ya=None):
+        if self.conv_math == "h2":
+            return ops.conv2d_h2(x, xa, self.h2[name], self.w[name + "_b"], 1, 0, residual, False, ya)
+        return ops.conv2d(x, self.w[name + "_w"], self.w[name + "_b"], 1, 0, residual, False)
+
+    def _lin(self, x, name, residual=None):
+        return ops.linear_ex(x, self.w[name + "_w"], self.w[name + "_b"], residual)
+
+    def __call__(self, x4, x4_amax=None, taps=None):
+        """x4 NHWC -> [B,1024].  x4_amax: x4's max-|x| record (f16x2 trunk).
+        taps: a dict that receives the intermediates X (encoder output), T0
+        (pooled tokens), tn, dec0, dec1 (tests)."""
+        w, m, nh, no = self.w, self.mid_dim, self.heads, self.n_obj
+        b, hh, ww, _ = x4.shape
+        n = hh * ww
+        h2 = self.conv_math == "h2"
+        rec = ops.amax_records(5, x4.device) if h2 else [None] * 5
+        if h2 and x4_amax is None:
+            x4_amax = ops.amax_f32(x4, rec[4])
+        x = self._conv(x4, x4_amax, "conv", None, rec[0])
+        qkv = self._conv(x, rec[0], "enc_qkv").view(b * n, 3 * m)
+        a = ops.attention_hd128(qkv[:, :m], qkv[:, m:2 * m], qkv[:, 2 * m:], b, n, n, nh).view(b, hh, ww, m)
+        if h2:
+            ops.amax_f32(a, rec[1])
+        x = self._conv(a, rec[1], "enc_proj", x, rec[2])
+        x = self._conv(x, rec[2], "enc_mlp", x, rec[3])
+        kv = self._conv(x, rec[3], "dec_kv").view(b * n, 4 * m)
+        t0 = ops.token_pool(x, w["query"])
+        t = ops.layernorm(self._lin(t0.view(b * no, m), "tn"), w["tn_g"], w["tn_beta"])
+        if taps is not None:
+            taps.update(X=x.view(b, n, m), T0=t0, tn=t.view(b, no, m))
+        for i in (0, 1):
+            p = f"d{i}_"
+            q = self._lin(ops.layernorm(t, w[p + "ln1_g"], w[p + "ln1_b"]), p + "cq")
+            ca = ops.attention_hd128(q, kv[:, 2 * i * m:(2 * i + 1) * m], kv[:, (2 * i + 1) * m:(2 * i + 2) * m], b, no,
+                                     n, nh)
+            t = self._lin(ca, p + "cproj", t)
+            hdn = self._lin(t, p + "fc1")
+            t = self._lin(ops.gelu(hdn, out=hdn), p + "fc2", t)
+            sq = self._lin(ops.layernorm(t, w[p + "ln2_g"], w[p + "ln2_b"]), p + "sqkv")
+            sa = ops.attention_hd128(sq[:, :m], sq[:, m:2 * m], sq[:, 2 * m:], b, no, no, nh)
+            t = self._lin(sa, p + "sproj", t)
+            if taps is not None:
+                taps[f"dec{i}"] = t.view(b, no, m)
+        return self._lin(t.view(b, no * m), "out")
+
+
+class Token(_Extractor):
+    """Token (networks/RetrievalNet.py:290-305, forward_test): backbone ->
+    Token_Refine(8 heads, 4 object tokens, mid_dim 1024, 1 encoder, 2 decoders)
+    -> F.normalize, 1024 values per image.  The network spca_train.py and the
+    training drivers construct.
+
+    Constructor: the reference's positional order (outputdim, classifier_num,
+    pretrained, backbone) first; classifier_num belongs to the ArcFace training
+    head and is accepted and ignored; pretrained weights cannot be downloaded,
+    so pretrained must stay None.  Then state_dict (trunk keys as
+    networks.ResNet accepts, head keys as weights.token_head_from_state_dict),
+    seed (synthetic weights when state_dict is None), device, conv_math and
+    stride_on as networks.SOLAR.  outputdim must be 1024 (mid_dim and the
+    width tr.proj emits)."""
+
+    in_channels = 4
+
+    def __init__(self, outputdim=1024, classifier_num=81313, pretrained=None, backbone="resnet101", state_dict=None,
+                 seed=0, device="cuda", conv_math="h2", stride_on="3x3"):
+        if outputdim != 1024:
+            raise ValueError("networks.Token requires outputdim == 1024 (Token_Refine's proj emits 1024 values, "
+                             "networks/RetrievalNet.py:173)")
+        if pretrained is not None:
+            raise ValueError("networks.Token: pretrained weights cannot be downloaded; pass state_dict")
+        self.device = torch.device(device)
+        if state_dict is None:
+            head = W.token_head_from_state_dict(W.synthetic_token_head(seed + 1))
+        else:
+            head = W.token_head_from_state_dict(state_dict)
+        self.backbone = ResNet(backbone, state_dict, seed, device, conv_math, stride_on)
+        if head["conv_w"].shape[-1] != self.backbone.outputdim_block5:
+            raise ValueError("networks.Token: tr.conv does not fit the trunk")
+        self.conv_math = conv_math
+        self.tr = Token_Refine(8, head["query"].shape[0], outputdim, 1, 2, head, device, conv_math)
+        self.outputdim = outputdim
+        self.meta = {"outputdim": outputdim}
+
+    def forward_test_nhwc(self, x_nhwc, hook=None):
+        if self.conv_math == "h2":
+            x4, x4a = self.backbone(x_nhwc, hook=hook, return_amax=True)
+        else:
+            x4, x4a = self.backbone(x_nhwc), None
+        return self.tail(self.tr(x4, x4a))
+
+    def tail(self, f):
+        """:304: F.normalize on the head's [B,1024]."""
+        return ops.l2_normalize(f, EPS_L2, out=f)
+
+
+class RetrievalNet(Token):
+    """RetrievalNet (networks/RetrievalNet.py:263-278): the same backbone, the
+    same Token_Refine head and the same forward_test as Token, with the
+    reference's (classifier_num) signature (its ArcFace_Delg classifier is
+    training-only and ignored).  The keyword arguments are Token's."""
+
+    def __init__(self, classifier_num=None, **kw):
+        super().__init__(1024, classifier_num, None, "resnet101", **kw)
+
+
 class ConvDimReduction:
     """PCA-whitening as a frozen 1x1 conv (networks/spca.py:205-227):
     weight = P[:dim], bias = -(P m)[:dim]."""

@@ -355,6 +355,79 @@ def soa_attention(fgh, c):
     return out
 
 
+def _rows128(t, rows, heads, name):
+    """A [rows, heads * 128] fp32 operand of attention_hd128: a 2-D tensor or a
+    column slice of one (unit column stride, any row stride) -> its row stride."""
+    if t.dtype != torch.float32:
+        raise TypeError(f"attention_hd128 {name}: expected float32, got {t.dtype}")
+    if t.dim() != 2 or tuple(t.shape) != (rows, heads * 128):
+        raise ValueError(f"attention_hd128 {name}: expected [{rows},{heads * 128}], got {tuple(t.shape)}")
+    ld = t.stride(0) if rows > 1 else max(t.stride(0), heads * 128)
+    if t.stride(1) != 1 or ld < heads * 128:
+        raise ValueError(f"attention_hd128 {name}: columns must be contiguous and rows at least {heads * 128} apart")
+    if ld % 4 or t.data_ptr() % 16:
+        raise ValueError(f"attention_hd128 {name}: row stride % 4 == 0 and a 16-B aligned first element")
+    return ld
+
+
+def attention_hd128(q, k, v, b, nq, nk, heads):
+    """Multi-head attention at head width 128 (rr_attention_hd128): q [b nq,
+    heads 128], k and v [b nk, heads 128], each a 2-D fp32 tensor or a column
+    slice of a wider one (e.g. qkv[:, :1024]) -> softmax(128^-0.5 q k^T) v,
+    dense [b nq, heads 128]."""
+    b, nq, nk, heads = int(b), int(nq), int(nk), int(heads)
+    if b < 0 or heads < 1 or not 1 <= nq <= 65535 or not 1 <= nk <= 65535:
+        raise ValueError("attention_hd128: b >= 0, heads >= 1, 1 <= nq, nk <= 65535")
+    ldq = _rows128(q, b * nq, heads, "q")
+    ldk = _rows128(k, b * nk, heads, "k")
+    ldv = _rows128(v, b * nk, heads, "v")
+    dev = _dev(q)
+    if k.device != q.device or v.device != q.device:
+        raise ValueError("attention_hd128: q, k and v must be on one device")
+    out = torch.empty((b * nq, heads * 128), dtype=torch.float32, device=q.device)
+    if b == 0:
+        return out
+    hd = _lib.handle(dev)
+    _lib.check(_lib.lib().rr_attention_hd128(hd, _ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, b, nq, nk, heads, _ptr(out),
+                                             _stream(dev)), hd, "rr_attention_hd128")
+    return out
+
+
+def token_pool(x, query):
+    """Object-token pooling (rr_token_pool): x [B,H,W,C] (or [B,HW,C]), query
+    [n_obj,C] -> [B,n_obj,C] = sum_p softmax_o(query_o . x_p) x_p, the softmax
+    over the objects."""
+    _f32(x, "token_pool x")
+    _f32(query, "token_pool query")
+    if x.dim() not in (3, 4) or query.dim() != 2 or query.shape[1] != x.shape[-1]:
+        raise ValueError(f"token_pool: x [B,H,W,C] or [B,HW,C] and query [n_obj,C], got {tuple(x.shape)} and "
+                         f"{tuple(query.shape)}")
+    b, c, n_obj = x.shape[0], x.shape[-1], query.shape[0]
+    if c % 256 or not 256 <= c <= 1024 or not 1 <= n_obj <= 8:
+        raise ValueError("token_pool: c % 256 == 0, 256 <= c <= 1024, 1 <= n_obj <= 8")
+    hw = x.numel() // (b * c) if b else 1
+    if hw < 1:
+        raise ValueError("token_pool: an empty map")
+    dev = _dev(x)
+    out = torch.empty((b, n_obj, c), dtype=torch.float32, device=x.device)
+    hd = _lib.handle(dev)
+    _lib.check(_lib.lib().rr_token_pool(hd, _ptr(x), b, hw, c, _ptr(query), n_obj, _ptr(out), _stream(dev)), hd,
+               "rr_token_pool")
+    return out
+
+
+def gelu(x, out=None):
+    """Exact (erf) GELU (rr_gelu), elementwise; out=x runs in place."""
+    _f32(x, "gelu")
+    y = torch.empty_like(x) if out is None else out
+    if y is not x and (y.dtype != torch.float32 or not y.is_contiguous() or y.numel() != x.numel()):
+        raise ValueError("gelu: out must be contiguous float32 of x's size")
+    dev = _dev(x)
+    hd = _lib.handle(dev)
+    _lib.check(_lib.lib().rr_gelu(hd, _ptr(x), x.numel(), _ptr(y), _stream(dev)), hd, "rr_gelu")
+    return y
+
+
 def cosine_topk_workspace_size(nq, n, d, k):
     return int(_lib.lib().rr_cosine_topk_workspace_size(int(nq), int(n), int(d), int(k)))
 

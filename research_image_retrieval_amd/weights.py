@@ -329,6 +329,169 @@ def synthetic_solar_head(seed, cin=2048, k=2):
     return sd
 
 
+# ---- Token head (networks/RetrievalNet.py:94-187) ---------------------------
+_BN_KEYS = ("weight", "bias", "running_mean", "running_var")
+_WB = ("weight", "bias")
+_ATT = tuple(f"{p}.{k}" for p in ("q", "k", "v", "proj") for k in _WB)
+
+
+def _token_head_keys(decoders=2):
+    ks = ["tr.query"]
+    ks += [f"tr.token_norm.{i}.{k}" for i in (0, 1) for k in _WB]
+    ks += [f"tr.encoder.0.attn.{k}" for k in _ATT]
+    ks += [f"tr.encoder.0.bn.{k}" for k in _BN_KEYS] + [f"tr.encoder.0.mlp.{k}" for k in _WB]
+    for i in range(decoders):
+        d = f"tr.decoder.{i}."
+        ks += [d + f"{a}.{k}" for a in ("self_attn", "cross_attn") for k in _ATT]
+        ks += [d + f"{n}.{k}" for n in ("bn1", "bn2", "mlp.fc1", "mlp.fc2") for k in _WB]
+    ks += [f"tr.conv.0.{k}" for k in _WB] + [f"tr.conv.1.{k}" for k in _BN_KEYS]
+    ks += [f"tr.proj.0.{k}" for k in _WB] + [f"tr.proj.1.{k}" for k in _BN_KEYS]
+    return tuple(ks)
+
+
+TOKEN_HEAD_KEYS = _token_head_keys()
+
+
+def token_head_from_state_dict(sd, eps=BN_EPS):
+    """The Token_Refine head of a reference Token / RetrievalNet checkpoint
+    (keys tr.*, TOKEN_HEAD_KEYS; a leading ``module.`` is dropped; trunk,
+    ``classifier.*`` and ``num_batches_tracked`` keys are ignored) as fp32
+    contiguous tensors.  Every fold is computed in float64 and rounded once.
+
+      conv_w [mid,1,1,2048], conv_b: tr.conv with its BatchNorm2d folded, the
+        conv's own bias included ((b - mean) s + beta, s = gamma / sqrt(var + eps));
+      enc_qkv_w [3 mid,1,1,mid], enc_qkv_b: the encoder's q | k | v stacked;
+      enc_proj_w [mid,1,1,mid], enc_proj_b;
+      enc_mlp_w, enc_mlp_b: the encoder's BatchNorm1d (x s + t per channel)
+        folded into its mlp: W o s on columns, b + W t;
+      query [n_obj, mid];  tn_w [mid,mid], tn_b, tn_g, tn_beta: token_norm;
+      dec_kv_w [4 mid,1,1,mid], dec_kv_b: the two decoders' cross-attention
+        k1 | v1 | k2 | v2 stacked (both read the encoder output);
+      per decoder i in (0, 1): d{i}_ln1_g/_b, d{i}_cq_w/_b, d{i}_cproj_w/_b,
+        d{i}_fc1_w/_b [2 mid,mid], d{i}_fc2_w/_b [mid,2 mid], d{i}_ln2_g/_b,
+        d{i}_sqkv_w [3 mid,mid] / _b (self-attention q | k | v), d{i}_sproj_w/_b;
+      out_w [1024, n_obj mid], out_b: tr.proj with its BatchNorm1d folded."""
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
+    missing = [k for k in TOKEN_HEAD_KEYS if k not in sd]
+    if missing:
+        raise ValueError(f"Token head: missing keys {missing}")
+    d = lambda k: sd["tr." + k].double()  # noqa: E731
+    f = lambda a: a.float().contiguous()  # noqa: E731
+    cw = sd["tr.conv.0.weight"]
+    if cw.dim() != 4 or tuple(cw.shape[2:]) != (1, 1):
+        raise ValueError(f"tr.conv.0.weight: expected [mid,2048,1,1], got {tuple(cw.shape)}")
+    mid, cin = cw.shape[0], cw.shape[1]
+    qy = sd["tr.query"]
+    if qy.dim() != 3 or qy.shape[0] != 1 or qy.shape[2] != mid:
+        raise ValueError(f"tr.query: expected [1,n_obj,{mid}], got {tuple(qy.shape)}")
+    n_obj = qy.shape[1]
+
+    def shape(k, want):
+        if tuple(sd["tr." + k].shape) != tuple(want):
+            raise ValueError(f"tr.{k}: expected {list(want)}, got {list(sd['tr.' + k].shape)}")
+
+    for a in ["encoder.0.attn"] + [f"decoder.{i}.{n}" for i in (0, 1) for n in ("self_attn", "cross_attn")]:
+        for p in ("q", "k", "v", "proj"):
+            shape(f"{a}.{p}.weight", (mid, mid))
+            shape(f"{a}.{p}.bias", (mid,))
+    shape("encoder.0.mlp.weight", (mid, mid))
+    shape("token_norm.0.weight", (mid, mid))
+    for i in (0, 1):
+        shape(f"decoder.{i}.mlp.fc1.weight", (2 * mid, mid))
+        shape(f"decoder.{i}.mlp.fc2.weight", (mid, 2 * mid))
+    shape("proj.0.weight", (sd["tr.proj.0.weight"].shape[0], n_obj * mid))
+
+    def bn(p):
+        s = d(p + ".weight") / torch.sqrt(d(p + ".running_var") + eps)
+        return s, d(p + ".bias") - d(p + ".running_mean") * s
+
+    as_conv = lambda w: f(w).reshape(w.shape[0], 1, 1, w.shape[1])  # noqa: E731
+    cat = lambda ks: torch.cat([d(k) for k in ks])  # noqa: E731
+    h = {}
+    s, t = bn("conv.1")
+    h["conv_w"] = f((d("conv.0.weight") * s[:, None, None, None]).permute(0, 2, 3, 1))
+    h["conv_b"] = f(d("conv.0.bias") * s + t)
+    e = "encoder.0."
+    h["enc_qkv_w"] = as_conv(cat([e + f"attn.{p}.weight" for p in "qkv"]))
+    h["enc_qkv_b"] = f(cat([e + f"attn.{p}.bias" for p in "qkv"]))
+    h["enc_proj_w"], h["enc_proj_b"] = as_conv(d(e + "attn.proj.weight")), f(d(e + "attn.proj.bias"))
+    s, t = bn(e + "bn")
+    h["enc_mlp_w"] = as_conv(d(e + "mlp.weight") * s[None, :])
+    h["enc_mlp_b"] = f(d(e + "mlp.bias") + d(e + "mlp.weight") @ t)
+    h["query"] = f(qy[0])
+    h["tn_w"], h["tn_b"] = f(d("token_norm.0.weight")), f(d("token_norm.0.bias"))
+    h["tn_g"], h["tn_beta"] = f(d("token_norm.1.weight")), f(d("token_norm.1.bias"))
+    kv = [f"decoder.{i}.cross_attn.{p}" for i in (0, 1) for p in "kv"]
+    h["dec_kv_w"] = as_conv(cat([k + ".weight" for k in kv]))
+    h["dec_kv_b"] = f(cat([k + ".bias" for k in kv]))
+    for i in (0, 1):
+        p, o = f"decoder.{i}.", f"d{i}_"
+        for src, dst in (("bn1", "ln1"), ("bn2", "ln2")):
+            h[o + dst + "_g"], h[o + dst + "_b"] = f(d(p + src + ".weight")), f(d(p + src + ".bias"))
+        for src, dst in (("cross_attn.q", "cq"), ("cross_attn.proj", "cproj"), ("mlp.fc1", "fc1"), ("mlp.fc2", "fc2"),
+                         ("self_attn.proj", "sproj")):
+            h[o + dst + "_w"], h[o + dst + "_b"] = f(d(p + src + ".weight")), f(d(p + src + ".bias"))
+        h[o + "sqkv_w"] = f(cat([p + f"self_attn.{n}.weight" for n in "qkv"]))
+        h[o + "sqkv_b"] = f(cat([p + f"self_attn.{n}.bias" for n in "qkv"]))
+    s, t = bn("proj.1")
+    h["out_w"] = f(d("proj.0.weight") * s[:, None])
+    h["out_b"] = f(d("proj.0.bias") * s + t)
+    return h
+
+
+def synthetic_token_head(seed, mid_dim=1024, n_obj=4):
+    """Seeded Token_Refine weights under the reference's keys (TOKEN_HEAD_KEYS):
+    q / k gains that put the attention logits near 10 on post-ReLU unit-variance
+    maps, an object query scaled so the slot softmax is neither uniform nor
+    one-hot, non-trivial BatchNorm running statistics and LayerNorm gamma /
+    beta, and NON-ZERO attention ``proj`` layers: the reference initialises them
+    to zero (:108-109), which would make every attention a no-op.  The fixture
+    generator loads them into the reference's modules; the tests fold them
+    (token_head_from_state_dict)."""
+    rs = np.random.RandomState(seed)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
+    m = mid_dim
+    sd = collections.OrderedDict()
+
+    def lin(key, out_dim, in_dim, gain=1.0, bias=0.1):
+        sd[key + ".weight"] = t(rs.standard_normal((out_dim, in_dim)) * (gain / np.sqrt(in_dim)))
+        sd[key + ".bias"] = t(rs.standard_normal(out_dim) * bias)
+
+    def norm(key, dim, stats):
+        sd[key + ".weight"] = t(rs.uniform(0.5, 1.5, dim))
+        sd[key + ".bias"] = t(rs.standard_normal(dim) * 0.1)
+        if stats:
+            sd[key + ".running_mean"] = t(rs.standard_normal(dim) * 0.1)
+            sd[key + ".running_var"] = t(rs.uniform(0.5, 1.5, dim))
+
+    def attention(key, qk_gain):
+        lin(key + ".q", m, m, qk_gain)
+        lin(key + ".k", m, m, qk_gain)
+        lin(key + ".v", m, m)
+        lin(key + ".proj", m, m)
+
+    sd["tr.query"] = t(rs.standard_normal((1, n_obj, m)) * (2.0 / np.sqrt(m)))
+    lin("tr.token_norm.0", m, m)
+    norm("tr.token_norm.1", m, False)
+    attention("tr.encoder.0.attn", 2.0)
+    norm("tr.encoder.0.bn", m, True)
+    lin("tr.encoder.0.mlp", m, m)
+    for i in range(2):
+        d = f"tr.decoder.{i}."
+        attention(d + "self_attn", 2.0)
+        attention(d + "cross_attn", 2.0)
+        norm(d + "bn1", m, False)
+        norm(d + "bn2", m, False)
+        lin(d + "mlp.fc1", 2 * m, m)
+        lin(d + "mlp.fc2", m, 2 * m)
+    sd["tr.conv.0.weight"] = t(rs.standard_normal((m, 2048, 1, 1)) / np.sqrt(2048))
+    sd["tr.conv.0.bias"] = t(rs.standard_normal(m) * 0.1)
+    norm("tr.conv.1", m, True)
+    lin("tr.proj.0", 1024, n_obj * m)
+    norm("tr.proj.1", 1024, True)
+    return sd
+
+
 def folded_resnet(sd, arch):
     """torchvision-keyed trunk -> ordered list of folded (name, w, b, stride, pad)."""
     def bn(prefix):
