@@ -69,7 +69,8 @@ typedef struct rr_handle_s* rr_handle_t;
  * rr_soa_attention (SOLAR's second-order attention block) was ADDED under 7
  * as well: no existing entry changed, so a caller built against the earlier
  * revision-7 header still passes the right arguments everywhere; likewise
- * rr_attention_hd128, rr_token_pool and rr_gelu (the Token head).
+ * rr_attention_hd128, rr_token_pool and rr_gelu (the Token head), and
+ * rr_how_vlad and rr_how_asmk (the HOW head's aggregations).
  * Bindings compare rr_abi_version() with the RR_ABI_VERSION they were
  * written against.                                                          */
 #define RR_ABI_VERSION 7
@@ -653,6 +654,54 @@ int rr_token_pool(rr_handle_t h, const float* x, int b, int hw, int c,
  * networks/RetrievalNet.py:67-72, 87); y may be x.  NaN stays NaN, +inf gives
  * +inf, -inf gives -0 (the limit).  Timing class 3.                         */
 int rr_gelu(rr_handle_t h, const float* x, long long n, float* y, void* stream);
+
+/* ---- HOW head (models/how_vlad.py) --------------------------------------- */
+/* VLAD pooling with a soft assignment, from the RAW local_proj rows: x
+ * [b][n][d] fp32 (NHWC rows of the 1x1 conv), centroids [k][d]; per image
+ *   x^_p = x_p / max(||x_p||_2, 1e-12)
+ *   dist[p][c] = sqrt(max(||x^_p||^2 + ||c||^2 - 2 x^_p . c, 0))
+ *   a[p][:] = softmax_c(-alpha dist[p][c])          (max subtracted)
+ *   out[c][:] = sum_p a[p][c] (x^_p - centroid_c)
+ * out [b][k * d].  Replaces HOWModel.extract_local_descriptors' F.normalize
+ * (models/how_vlad.py:162) and VLADPooling.forward's cdist, softmax and loop
+ * over the centroids (:36-55).  The final F.normalize over the k * d values
+ * (:56) is NOT fused: launch rr_l2_normalize(out, b, k * d) afterwards.
+ * x is read once; the normalised rows, the distances and the assignment never
+ * reach global memory; x^ . C^T and A^T . x^ run on the exact-fp32 MFMA.  A
+ * distance whose square rounds below zero is clamped to 0 (a descriptor equal
+ * to a centroid never gives NaN); an all-zero row gives x^ = 0.  No float
+ * atomics: where few images leave the chip short of work an image's positions
+ * are split over workgroups (a function of b and n only: at least 64 positions
+ * each, about 256 workgroups wanted) and the partial sums, kept in a
+ * per-stream buffer the library owns, are added in a fixed order: the same
+ * bits on every run, and for an image alone or in a batch wherever both
+ * choose the same split (any n <= 64 ceil(256 / b); never split at n <= 64).
+ * 1 <= k <= 128, d % 32 == 0, 32 <= d <= 256, 1 <= n <= 65535, x / centroids /
+ * out 16-B aligned (else RR_EINVAL, nothing written); b == 0 is RR_OK and
+ * writes nothing; offsets are 64-bit.  Timing class 3.                      */
+int rr_how_vlad(rr_handle_t h, const float* x, int b, int n, int d,
+                const float* centroids, int k, float alpha, float* out,
+                void* stream);
+
+/* ASMK's thresholded nearest-centroid histogram from the same raw rows:
+ * the normalisation and distances of rr_how_vlad, then per position the
+ * nearest centroid (the lowest index among equal distances, as torch.argmin)
+ * and its distance m_p; per image thr = mean_p m_p + std_p m_p (the unbiased
+ * std, / (n - 1), both in double); out [b][k],
+ *   out[c] = weights[c] * #{p : nearest(p) == c and m_p < thr}.
+ * Replaces :162 and ASMKPooling.forward's cdist, argmin, gather, threshold
+ * and double loop (:80-99); the F.normalize of :102 is the caller's
+ * rr_l2_normalize.  n == 1 gives a zero row (the std of one value is NaN and
+ * no comparison holds), and so do equal minima (std 0).  The count is an
+ * integer and is multiplied by the weight once, so the result depends on
+ * neither the order of the positions nor the split.  x is read once; the
+ * minima and indices pass through a per-stream buffer the library owns
+ * (8 bytes a position) to a second launch, one workgroup per image.
+ * Limits, alignment (weights included), b == 0 and the timing class are
+ * rr_how_vlad's.                                                            */
+int rr_how_asmk(rr_handle_t h, const float* x, int b, int n, int d,
+                const float* centroids, const float* weights, int k,
+                float* out, void* stream);
 
 #ifdef __cplusplus
 }

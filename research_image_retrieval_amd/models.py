@@ -4,6 +4,9 @@ Mirrors models/gem_pooling.py:12-143 and models/wrappers.py:18-90 for the GeM
 family named by the hot path: ``get_model('gem_r50' | 'gem_r101', num_classes,
 feature_dim=..., gem_p=...)`` returns a wrapper whose
 ``extract_global_descriptor(x)`` yields L2-normalised [B, feature_dim] fp32.
+The HOW family (models/how_vlad.py:14-287) is served the same way:
+``get_model('how_vlad_r50' | 'how_vlad_r101' | 'how_asmk_r50' | 'how_asmk_r101',
+num_classes, local_dim=..., num_clusters=...)``, [B, 2048] descriptors.
 Training (``forward(x, targets)`` losses, optimizers) is out of scope
 (SURVEY.md §2 row 13): ``forward`` only produces eval-mode logits.
 """
@@ -116,16 +119,181 @@ def get_gem_model(num_classes, backbone="resnet50", **kwargs):
     return GeMWrapper(num_classes=num_classes, backbone=backbone, **kwargs)
 
 
+class HOWModel(_Extractor):
+    """models/how_vlad.py:107-199, eval mode: resnet trunk -> local_proj (1x1
+    conv 2048 -> local_dim, +bias) -> F.normalize per position -> VLADPooling
+    (alpha = 100) or ASMKPooling -> final_proj Linear(K D or K, 2048);
+    extract_descriptor adds F.normalize.
+
+    Launches after the trunk: the 1x1 conv (conv_math "h2": the f16x2 core on
+    the trunk's max-|x| record; "f32": rr_conv2d), rr_how_vlad or rr_how_asmk on
+    its RAW rows (the per-position normalisation, the distances, the assignment
+    and the aggregation in one read), rr_l2_normalize over the pooled vector
+    (:56, :102), rr_linear, rr_l2_normalize.
+
+    Constructor: the reference's (backbone, pretrained, num_classes, local_dim,
+    pooling_type, num_clusters), then state_dict (trunk keys as networks.ResNet
+    accepts, the reference's index-named nn.Sequential keys included; head
+    keys as weights.how_head_from_state_dict), seed (synthetic weights when
+    state_dict is None), device, conv_math and stride_on as GeMModel."""
+
+    in_channels = 4
+    alpha = 100.0  # VLADPooling's default (:17); HOWModel never passes another
+
+    def __init__(self, backbone="resnet50", pretrained=False, num_classes=1000, local_dim=128, pooling_type="vlad",
+                 num_clusters=64, state_dict=None, seed=0, device="cuda", conv_math="h2", stride_on="3x3"):
+        if pretrained:
+            raise ValueError("pretrained weights need a download; pass a local state_dict instead "
+                             "(models/how_vlad.py:110 defaults to pretrained=True)")
+        if backbone not in ("resnet50", "resnet101"):
+            raise ValueError(f"Unsupported backbone: {backbone}")
+        if pooling_type not in ("vlad", "asmk"):
+            raise ValueError(f"Unsupported pooling type: {pooling_type}")
+        if local_dim % 32 or not 32 <= local_dim <= 256 or not 1 <= num_clusters <= 128:
+            raise ValueError("HOWModel: local_dim % 32 == 0, 32 <= local_dim <= 256, 1 <= num_clusters <= 128 "
+                             "(rr_how_vlad / rr_how_asmk)")
+        if state_dict is None:
+            head = W.how_head_from_state_dict(W.synthetic_how_head(seed + 1, pooling_type, local_dim, num_clusters,
+                                                                   num_classes))
+        else:
+            head = W.how_head_from_state_dict(state_dict)
+        if ("weights" in head) != (pooling_type == "asmk"):
+            raise ValueError(f"HOWModel: the state dict's head is not a {pooling_type} head")
+        if tuple(head["centroids"].shape) != (num_clusters, local_dim) or head["final_w"].shape[0] != 2048:
+            raise ValueError("HOWModel: head weight shapes do not fit local_dim and num_clusters")
+        self.device = torch.device(device)
+        self.conv_math = conv_math
+        self.pooling_type = pooling_type
+        self.backbone = ResNet(backbone, state_dict, seed, device, conv_math=conv_math, stride_on=stride_on)
+        if head["local_w"].shape[1] != self.backbone.outputdim_block5:
+            raise ValueError("HOWModel: local_proj does not fit the trunk")
+        self.w = {k: v.to(self.device) for k, v in head.items()}
+        self.local_w = self.w["local_w"].view(local_dim, 1, 1, -1)
+        self.local_h2 = ops.H2Conv(self.local_w) if conv_math == "h2" else None
+        self.local_dim, self.num_clusters = local_dim, num_clusters
+        self.outputdim = 2048
+
+    def local_map(self, x4, x4_amax=None):
+        """The raw local_proj output [B,H,W,local_dim] of a trunk map x4 NHWC."""
+        if self.conv_math == "h2":
+            if x4_amax is None:
+                x4_amax = ops.amax_f32(x4, ops.amax_records(1, x4.device)[0])
+            return ops.conv2d_h2(x4, x4_amax, self.local_h2, self.w["local_b"], 1, 0, None, False)
+        return ops.conv2d(x4, self.local_w, self.w["local_b"], 1, 0, None, False)
+
+    def head(self, x4, x4_amax=None, taps=None):
+        """x4 NHWC -> features [B,2048] (:155-175).  taps: a dict that receives
+        local (the raw local_proj rows [B,N,D]), pooled (after its L2) and
+        features (tests)."""
+        y = self.local_map(x4, x4_amax)
+        if self.pooling_type == "vlad":
+            v = ops.how_vlad(y, self.w["centroids"], self.alpha)
+        else:
+            v = ops.how_asmk(y, self.w["centroids"], self.w["weights"])
+        v = ops.l2_normalize(v, EPS_L2, out=v)
+        f = ops.linear(v, self.w["final_w"], self.w["final_b"])
+        if taps is not None:
+            taps.update(local=y.view(y.shape[0], -1, y.shape[-1]), pooled=v, features=f)
+        return f
+
+    def _trunk(self, x_nhwc, hook=None):
+        if self.conv_math == "h2":
+            return self.backbone(x_nhwc, hook=hook, return_amax=True)
+        return self.backbone(x_nhwc), None
+
+    def extract_features_nhwc(self, x_nhwc, hook=None):
+        return self.head(*self._trunk(x_nhwc, hook))
+
+    @torch.no_grad()
+    def extract_local_descriptors(self, x):
+        """L2-normalised local descriptors [B,N,D] (:149-164), for callers: the
+        pooling kernels normalise on load and never write these."""
+        y = self.local_map(*self._trunk(self._input(x)))
+        b, d = y.shape[0], y.shape[-1]
+        return ops.l2_normalize(y.view(-1, d), EPS_L2).view(b, -1, d)
+
+    @torch.no_grad()
+    def extract_features(self, x):
+        return self.extract_features_nhwc(self._input(x))
+
+    def forward_test_nhwc(self, x_nhwc, hook=None):
+        f = self.extract_features_nhwc(x_nhwc, hook)
+        return ops.l2_normalize(f, EPS_L2, out=f)
+
+    @torch.no_grad()
+    def extract_descriptor(self, x):
+        return self.forward_test(x)
+
+    @torch.no_grad()
+    def forward(self, x, targets=None):
+        feats = self.extract_features(x)
+        return None, ops.linear(feats, self.w["cls_w"], self.w["cls_b"])
+
+    __call__ = forward
+
+
+class _HOWWrapper(_Extractor):
+    """models/how_vlad.py:202-255: training-loop facade over HOWModel."""
+
+    in_channels = 4
+    pooling_type = None
+
+    def __init__(self, num_classes, backbone="resnet50", local_dim=128, num_clusters=64, **kw):
+        self.backbone = HOWModel(backbone=backbone, num_classes=num_classes, local_dim=local_dim,
+                                 pooling_type=self.pooling_type, num_clusters=num_clusters, **kw)
+        self.outputdim = self.backbone.outputdim
+
+    def forward_test_nhwc(self, x_nhwc, hook=None):
+        return self.backbone.forward_test_nhwc(x_nhwc, hook)
+
+    @torch.no_grad()
+    def forward(self, x, targets=None):
+        return self.backbone(x)
+
+    __call__ = forward
+
+    def extract_local_descriptors(self, x):
+        return self.backbone.extract_local_descriptors(x)
+
+    def extract_features(self, x):
+        return self.backbone.extract_features(x)
+
+    def extract_descriptor(self, x):
+        return self.backbone.extract_descriptor(x)
+
+    def extract_global_descriptor(self, x):
+        return self.backbone.extract_descriptor(x)
+
+
+class HOWVLADWrapper(_HOWWrapper):
+    pooling_type = "vlad"
+
+
+class HOWASMKWrapper(_HOWWrapper):
+    pooling_type = "asmk"
+
+
+def get_how_vlad_model(num_classes, backbone="resnet50", **kwargs):
+    return HOWVLADWrapper(num_classes=num_classes, backbone=backbone, **kwargs)
+
+
+def get_how_asmk_model(num_classes, backbone="resnet50", **kwargs):
+    return HOWASMKWrapper(num_classes=num_classes, backbone=backbone, **kwargs)
+
+
 MODEL_REGISTRY = {
     "gem_r50": lambda num_classes, **kw: get_gem_model(num_classes, backbone="resnet50", **kw),
     "gem_r101": lambda num_classes, **kw: get_gem_model(num_classes, backbone="resnet101", **kw),
+    "how_vlad_r50": lambda num_classes, **kw: get_how_vlad_model(num_classes, backbone="resnet50", **kw),
+    "how_vlad_r101": lambda num_classes, **kw: get_how_vlad_model(num_classes, backbone="resnet101", **kw),
+    "how_asmk_r50": lambda num_classes, **kw: get_how_asmk_model(num_classes, backbone="resnet50", **kw),
+    "how_asmk_r101": lambda num_classes, **kw: get_how_asmk_model(num_classes, backbone="resnet101", **kw),
 }
 
 # Other Table-1 methods exist in the reference registry (models/wrappers.py:22-50)
 # but are outside this build's hot path (SURVEY.md §2 rows 10-12).
-OUT_OF_SCOPE = ("delg_r50", "delg_r101", "token_r50", "token_r101", "how_vlad_r50", "how_vlad_r101",
-                "how_asmk_r50", "how_asmk_r101", "senet_g2_50", "senet_g2_101", "sosnet_r50", "sosnet_r101",
-                "spoc_r50", "spoc_r101")
+OUT_OF_SCOPE = ("delg_r50", "delg_r101", "token_r50", "token_r101", "senet_g2_50", "senet_g2_101", "sosnet_r50",
+                "sosnet_r101", "spoc_r50", "spoc_r101")
 
 
 def get_model(model_name, num_classes, **kwargs):

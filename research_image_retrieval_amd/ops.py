@@ -416,6 +416,58 @@ def token_pool(x, query):
     return out
 
 
+def _how_args(name, x, centroids):
+    _f32(x, f"{name} x")
+    _f32(centroids, f"{name} centroids")
+    if x.dim() not in (3, 4) or centroids.dim() != 2 or centroids.shape[1] != x.shape[-1]:
+        raise ValueError(f"{name}: x [B,N,D] or [B,H,W,D] and centroids [K,D], got {tuple(x.shape)} and "
+                         f"{tuple(centroids.shape)}")
+    b, d, k = x.shape[0], x.shape[-1], centroids.shape[0]
+    if d % 32 or not 32 <= d <= 256 or not 1 <= k <= 128:
+        raise ValueError(f"{name}: d % 32 == 0, 32 <= d <= 256, 1 <= k <= 128")
+    n = x.numel() // (b * d) if b else 1
+    if not 1 <= n <= 65535:
+        raise ValueError(f"{name}: 1 <= positions <= 65535")
+    if centroids.device != x.device:
+        raise ValueError(f"{name}: x and centroids must be on one device")
+    return b, n, d, k
+
+
+def how_vlad(x, centroids, alpha=100.0):
+    """HOW's VLAD pooling (rr_how_vlad): x [B,N,D] (or NHWC [B,H,W,D]), the RAW
+    local_proj rows, centroids [K,D] -> [B, K D] = sum_p softmax_c(-alpha
+    ||x^_p - c||)[c] (x^_p - c) with x^ = x / max(||x||, 1e-12).  The final L2 over
+    the K D values is the caller's l2_normalize."""
+    b, n, d, k = _how_args("how_vlad", x, centroids)
+    dev = _dev(x)
+    out = torch.empty((b, k * d), dtype=torch.float32, device=x.device)
+    if b == 0:
+        return out
+    hd = _lib.handle(dev)
+    _lib.check(_lib.lib().rr_how_vlad(hd, _ptr(x), b, n, d, _ptr(centroids), k, float(alpha), _ptr(out), _stream(dev)),
+               hd, "rr_how_vlad")
+    return out
+
+
+def how_asmk(x, centroids, weights):
+    """HOW's ASMK pooling (rr_how_asmk): x as how_vlad's, centroids [K,D],
+    weights [K] -> [B,K], weights[c] x the number of positions nearest to
+    centroid c whose distance is below the image's mean + std of those
+    distances.  The final L2 is the caller's l2_normalize."""
+    b, n, d, k = _how_args("how_asmk", x, centroids)
+    _f32(weights, "how_asmk weights")
+    if weights.dim() != 1 or weights.shape[0] != k or weights.device != x.device:
+        raise ValueError(f"how_asmk: weights must be [{k}] on x's device, got {tuple(weights.shape)}")
+    dev = _dev(x)
+    out = torch.empty((b, k), dtype=torch.float32, device=x.device)
+    if b == 0:
+        return out
+    hd = _lib.handle(dev)
+    _lib.check(_lib.lib().rr_how_asmk(hd, _ptr(x), b, n, d, _ptr(centroids), _ptr(weights), k, _ptr(out), _stream(dev)),
+               hd, "rr_how_asmk")
+    return out
+
+
 def gelu(x, out=None):
     """Exact (erf) GELU (rr_gelu), elementwise; out=x runs in place."""
     _f32(x, "gelu")

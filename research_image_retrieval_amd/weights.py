@@ -329,8 +329,84 @@ def synthetic_solar_head(seed, cin=2048, k=2):
     return sd
 
 
+# ---- HOW head (models/how_vlad.py:107-199) ----------------------------------
+HOW_HEAD_KEYS = ("local_proj.weight", "local_proj.bias", "pooling.centroids", "final_proj.weight", "final_proj.bias",
+                 "classifier.weight", "classifier.bias")
+
+
+def how_head_from_state_dict(sd):
+    """The HOW head of a reference checkpoint (HOWModel's keys local_proj.*,
+    pooling.centroids, pooling.weights for ASMK, final_proj.*, classifier.*,
+    bare or under the wrapper's leading ``backbone.``, a ``module.`` before
+    either dropped; trunk keys are ignored) as fp32 contiguous tensors:
+
+      local_w [D,2048] (the 1x1 conv flattened), local_b [D], centroids [K,D],
+      weights [K] (ASMK only: its presence says which pooling the head is),
+      final_w [2048, K D or K], final_b, cls_w [classes,2048], cls_b."""
+    flat = {}
+    for k, v in sd.items():
+        for lead in ("module.", "backbone."):
+            if k.startswith(lead):
+                k = k[len(lead):]
+        flat.setdefault(k, v)
+    missing = [k for k in HOW_HEAD_KEYS if k not in flat]
+    if missing:
+        raise ValueError(f"HOW head: missing keys {missing}")
+    lw, cent, fw, cw = (flat[k] for k in ("local_proj.weight", "pooling.centroids", "final_proj.weight",
+                                          "classifier.weight"))
+    if lw.dim() != 4 or tuple(lw.shape[2:]) != (1, 1):
+        raise ValueError(f"local_proj.weight: expected [D,Cin,1,1], got {tuple(lw.shape)}")
+    if cent.dim() != 2 or cent.shape[1] != lw.shape[0]:
+        raise ValueError(f"pooling.centroids: expected [K,{lw.shape[0]}], got {tuple(cent.shape)}")
+    asmk = "pooling.weights" in flat
+    pooled = cent.shape[0] if asmk else cent.shape[0] * cent.shape[1]
+    if fw.dim() != 2 or fw.shape[1] != pooled:
+        raise ValueError(f"final_proj.weight: expected [out,{pooled}], got {tuple(fw.shape)}")
+    if cw.dim() != 2 or cw.shape[1] != fw.shape[0]:
+        raise ValueError(f"classifier.weight: expected [classes,{fw.shape[0]}], got {tuple(cw.shape)}")
+    f = lambda a: a.float().contiguous()  # noqa: E731
+    head = {"local_w": f(lw.reshape(lw.shape[0], lw.shape[1])), "local_b": f(flat["local_proj.bias"]),
+            "centroids": f(cent), "final_w": f(fw), "final_b": f(flat["final_proj.bias"]),
+            "cls_w": f(cw), "cls_b": f(flat["classifier.bias"])}
+    if asmk:
+        if tuple(flat["pooling.weights"].shape) != (cent.shape[0],):
+            raise ValueError(f"pooling.weights: expected [{cent.shape[0]}], got {tuple(flat['pooling.weights'].shape)}")
+        head["weights"] = f(flat["pooling.weights"])
+    return head
+
+
+def synthetic_how_head(seed, pooling, local_dim=128, num_clusters=64, num_classes=8):
+    """Seeded HOW head weights under HOWModel's keys (HOW_HEAD_KEYS, plus
+    pooling.weights for pooling == "asmk").  The centroids are unit-norm random
+    directions, not the constructor's U(0,1) draws (:24-28): against unit-norm
+    descriptors at alpha = 100 the U(0,1) table (norms of about 6.5, logits
+    spread over tens of units) pushes the assignments towards one-hots (median
+    top weight 0.97 on random rows, against 0.8 for unit-norm centroids), and
+    only a soft assignment exercises the softmax; unit-norm centroids are also
+    what centroids trained on unit-norm descriptors look like.  ASMK's weights are
+    0.5 + U(0,1), not the constructor's ones (:73), so a wrong index shows."""
+    if pooling not in ("vlad", "asmk"):
+        raise ValueError(f"Unsupported pooling type: {pooling}")
+    rs = np.random.RandomState(seed)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
+    pooled = num_clusters * local_dim if pooling == "vlad" else num_clusters
+    sd = collections.OrderedDict()
+    sd["local_proj.weight"] = t(rs.standard_normal((local_dim, 2048, 1, 1)) / np.sqrt(2048))
+    sd["local_proj.bias"] = t(rs.standard_normal(local_dim) * 0.1)
+    c = rs.standard_normal((num_clusters, local_dim))
+    sd["pooling.centroids"] = t(c / np.linalg.norm(c, axis=1, keepdims=True))
+    if pooling == "asmk":
+        sd["pooling.weights"] = t(0.5 + rs.uniform(0, 1, num_clusters))
+    s = 1.0 / np.sqrt(pooled)
+    sd["final_proj.weight"] = t(rs.uniform(-1, 1, (2048, pooled)) * s)
+    sd["final_proj.bias"] = t(rs.uniform(-1, 1, 2048) * s)
+    sd["classifier.weight"] = t(rs.uniform(-1, 1, (num_classes, 2048)) / np.sqrt(2048))
+    sd["classifier.bias"] = t(rs.uniform(-1, 1, num_classes) / np.sqrt(2048))
+    return sd
+
+
 # ---- Token head (networks/RetrievalNet.py:94-187) ---------------------------
-_BN_KEYS = ("weight", "bias", "running_mean", "running_var")
+_BN_KEYS =("weight", "bias", "running_mean", "running_var")
 _WB = ("weight", "bias")
 _ATT = tuple(f"{p}.{k}" for p in ("q", "k", "v", "proj") for k in _WB)
 
