@@ -578,9 +578,11 @@ int rr_l2_normalize(rr_handle_t h, const float* x, int m, int d, float eps,
  * c % 256 == 0, c <= 2048, hw > 0, y / w2 / out 16-B aligned (else RR_EINVAL);
  * b == 0 is RR_OK with no launch.  No float atomics: where few images leave
  * the chip short of work, an image's pixels are split over workgroups whose
- * partial sums go to a buffer the handle keeps per stream (allocated on first
- * use) and are added in a fixed order; the split depends on (b, hw) alone, so
- * the result is the same bits on every run.                                 */
+ * partial sums go to the heads' scratch and are added in a fixed order; the
+ * split depends on (b, hw) alone, so the result is the same bits on every run.
+ * The heads' scratch: a per-stream buffer the handle owns (allocated on first
+ * use, grown on demand), shared by rr_dolg_local_pool, rr_token_pool,
+ * rr_how_vlad and rr_how_asmk and freed by rr_destroy.                      */
 int rr_dolg_local_pool(rr_handle_t h, const float* y, int b, int hw, int c,
                        const float* w2, float b2, float* out, void* stream);
 
@@ -640,11 +642,11 @@ int rr_attention_hd128(rr_handle_t h, const float* q, long long ldq,
  * the softmax over the n_obj OBJECTS of each position (max subtracted), no
  * scale.  x is read once.  No float atomics: where few images leave the chip
  * short of work an image's positions are split over workgroups (a function of
- * b and hw only) and the partial sums, kept in a per-stream buffer the library
- * owns, are added in a fixed order: the same bits on every run, and for an
- * image alone or in a batch wherever both choose the same split (at least 16
- * positions per workgroup, about 1024 workgroups wanted: any hw <= 16 *
- * ceil(1024 / b)).
+ * b and hw only) and the partial sums, kept in the heads' scratch
+ * (rr_dolg_local_pool), are added in a fixed order: the same bits on every
+ * run, and for an image alone or in a batch wherever both choose the same
+ * split (at least 16 positions per workgroup, about 1024 workgroups wanted:
+ * any hw <= 16 * ceil(1024 / b)).
  * c % 256 == 0, 256 <= c <= 1024, 1 <= n_obj <= 8, hw >= 1, x / query / out
  * 16-B aligned (else RR_EINVAL); b == 0 is RR_OK.  Timing class 3.          */
 int rr_token_pool(rr_handle_t h, const float* x, int b, int hw, int c,
@@ -672,8 +674,8 @@ int rr_gelu(rr_handle_t h, const float* x, long long n, float* y, void* stream);
  * to a centroid never gives NaN); an all-zero row gives x^ = 0.  No float
  * atomics: where few images leave the chip short of work an image's positions
  * are split over workgroups (a function of b and n only: at least 64 positions
- * each, about 256 workgroups wanted) and the partial sums, kept in a
- * per-stream buffer the library owns, are added in a fixed order: the same
+ * each, about 256 workgroups wanted) and the partial sums, kept in the heads'
+ * scratch (rr_dolg_local_pool), are added in a fixed order: the same
  * bits on every run, and for an image alone or in a batch wherever both
  * choose the same split (any n <= 64 ceil(256 / b); never split at n <= 64).
  * 1 <= k <= 128, d % 32 == 0, 32 <= d <= 256, 1 <= n <= 65535, x / centroids /
@@ -695,8 +697,8 @@ int rr_how_vlad(rr_handle_t h, const float* x, int b, int n, int d,
  * no comparison holds), and so do equal minima (std 0).  The count is an
  * integer and is multiplied by the weight once, so the result depends on
  * neither the order of the positions nor the split.  x is read once; the
- * minima and indices pass through a per-stream buffer the library owns
- * (8 bytes a position) to a second launch, one workgroup per image.
+ * minima and indices pass through the heads' scratch (rr_dolg_local_pool;
+ * 8 bytes a position) to a second launch, one workgroup per image.
  * Limits, alignment (weights included), b == 0 and the timing class are
  * rr_how_vlad's.                                                            */
 int rr_how_asmk(rr_handle_t h, const float* x, int b, int n, int d,

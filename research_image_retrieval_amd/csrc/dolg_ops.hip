@@ -7,14 +7,9 @@
 //   fl = att * fmn; proj = fg (fg . fl_p) / ||fg||^2; fo = mean_p (fl - proj)
 // proj is linear in fl, so fo = m - fg (fg . m) / (fg . fg) with m = mean_p fl:
 // neither fl nor proj is ever stored.
-#include <map>
-#include <mutex>
-
-#include "rr_internal.hpp"
+#include "heads_common.hpp"
 
 namespace rr {
-
-typedef float dolg_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kPoolWaves = 4;        // waves per workgroup (256 threads)
 constexpr int kPoolMinPixels = 8;    // fewest pixels a workgroup takes when an image is split
@@ -28,7 +23,7 @@ constexpr int kPoolTargetBlocks = 1024;  // workgroups wanted before images stop
 // image * splits + s takes pixels [s chunk, (s + 1) chunk) of its image, wave
 // w of it every kPoolWaves-th pixel from s chunk + w; the waves' accumulators
 // are added through LDS in wave order.  splits == 1: out[image] = sum / hw.
-// Otherwise the sum goes to part[image][s] and dolg_pool_sum_kernel adds an
+// Otherwise the sum goes to part[image][s] and slab_sum_kernel<true> adds an
 // image's slabs in a fixed order: the same bits on every run (no float atomics).
 template <int NV>
 __global__ __launch_bounds__(kPoolWaves * 64) void dolg_local_pool_kernel(const float* __restrict__ y, int hw, int chunk,
@@ -42,24 +37,24 @@ __global__ __launch_bounds__(kPoolWaves * 64) void dolg_local_pool_kernel(const 
   const int p1 = p0 + chunk < hw ? p0 + chunk : hw;
   const float* yi = y + (long long)img * hw * C + lane * 4;
 
-  dolg_f32x4 wv[NV], acc[NV], cur[NV], nxt[NV];
+  f32x4 wv[NV], acc[NV], cur[NV], nxt[NV];
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
-    wv[j] = *reinterpret_cast<const dolg_f32x4*>(w2 + j * 256 + lane * 4);
-    acc[j] = dolg_f32x4{0.f, 0.f, 0.f, 0.f};
-    cur[j] = dolg_f32x4{0.f, 0.f, 0.f, 0.f};
-    nxt[j] = dolg_f32x4{0.f, 0.f, 0.f, 0.f};
+    wv[j] = *reinterpret_cast<const f32x4*>(w2 + j * 256 + lane * 4);
+    acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    cur[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    nxt[j] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   int p = p0 + wave;  // wave-uniform
   if (p < p1) {
 #pragma unroll
-    for (int j = 0; j < NV; ++j) cur[j] = *reinterpret_cast<const dolg_f32x4*>(yi + (long long)p * C + j * 256);
+    for (int j = 0; j < NV; ++j) cur[j] = *reinterpret_cast<const f32x4*>(yi + (long long)p * C + j * 256);
   }
   for (; p < p1; p += kPoolWaves) {
     const int pn = p + kPoolWaves;
     if (pn < p1) {  // the next row's loads fly under this row's arithmetic
 #pragma unroll
-      for (int j = 0; j < NV; ++j) nxt[j] = *reinterpret_cast<const dolg_f32x4*>(yi + (long long)pn * C + j * 256);
+      for (int j = 0; j < NV; ++j) nxt[j] = *reinterpret_cast<const f32x4*>(yi + (long long)pn * C + j * 256);
     }
     float ss = 0.f, dot = 0.f;
 #pragma unroll
@@ -85,7 +80,7 @@ __global__ __launch_bounds__(kPoolWaves * 64) void dolg_local_pool_kernel(const 
   if (wave > 0) {
 #pragma unroll
     for (int j = 0; j < NV; ++j)
-      *reinterpret_cast<dolg_f32x4*>(dolg_lds + (wave - 1) * C + j * 256 + lane * 4) = acc[j];
+      *reinterpret_cast<f32x4*>(dolg_lds + (wave - 1) * C + j * 256 + lane * 4) = acc[j];
   }
   __syncthreads();
   if (wave == 0) {
@@ -93,36 +88,12 @@ __global__ __launch_bounds__(kPoolWaves * 64) void dolg_local_pool_kernel(const 
     float* o = dst + (long long)blockIdx.x * C + lane * 4;  // out[img] (splits == 1) or part[img][s]
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
-      dolg_f32x4 t = acc[j];
+      f32x4 t = acc[j];
 #pragma unroll
-      for (int w = 0; w < kPoolWaves - 1; ++w) t += *reinterpret_cast<const dolg_f32x4*>(dolg_lds + w * C + j * 256 + lane * 4);
+      for (int w = 0; w < kPoolWaves - 1; ++w) t += *reinterpret_cast<const f32x4*>(dolg_lds + w * C + j * 256 + lane * 4);
       if (splits == 1) t = t / den;
-      *reinterpret_cast<dolg_f32x4*>(o + j * 256) = t;
+      *reinterpret_cast<f32x4*>(o + j * 256) = t;
     }
-  }
-}
-
-// out[img][c] = (sum_s part[img][s][c]) / hw in a fixed order: workgroup
-// (image, 256-channel group), wave w adds slabs w, w + 16, ... in that order
-// (1 KiB per wave load), then the waves' sums are added through LDS in wave
-// order.
-constexpr int kSumWaves = 16;
-__global__ __launch_bounds__(kSumWaves * 64) void dolg_pool_sum_kernel(const float* __restrict__ part, int splits, int c,
-                                                                       int hw, float* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) float red[(kSumWaves - 1) * 256];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int groups = c >> 8;
-  const int img = blockIdx.x / groups, g = blockIdx.x - img * groups;
-  const float* pp = part + (long long)img * splits * c + g * 256 + lane * 4;
-  dolg_f32x4 t = dolg_f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-  for (int s = wave; s < splits; s += kSumWaves) t += *reinterpret_cast<const dolg_f32x4*>(pp + (long long)s * c);
-  if (wave > 0) *reinterpret_cast<dolg_f32x4*>(red + (wave - 1) * 256 + lane * 4) = t;
-  __syncthreads();
-  if (wave == 0) {
-#pragma unroll
-    for (int w = 0; w < kSumWaves - 1; ++w) t += *reinterpret_cast<const dolg_f32x4*>(red + w * 256 + lane * 4);
-    *reinterpret_cast<dolg_f32x4*>(out + (long long)img * c + g * 256 + lane * 4) = t / (float)hw;
   }
 }
 
@@ -138,8 +109,8 @@ __global__ __launch_bounds__(256) void dolg_orth_fuse_kernel(const float* __rest
   float* o = out + (long long)row * 2 * c;
   float gm = 0.f, gg = 0.f;
   for (int i = lane * 4; i < c; i += 256) {
-    const dolg_f32x4 gv = *reinterpret_cast<const dolg_f32x4*>(g + i);
-    const dolg_f32x4 mv = *reinterpret_cast<const dolg_f32x4*>(mr + i);
+    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i);
+    const f32x4 mv = *reinterpret_cast<const f32x4*>(mr + i);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       gm = fmaf(gv[e], mv[e], gm);
@@ -150,54 +121,10 @@ __global__ __launch_bounds__(256) void dolg_orth_fuse_kernel(const float* __rest
   gg = wave_sum(gg);
   const float k = gm / gg;
   for (int i = lane * 4; i < c; i += 256) {
-    const dolg_f32x4 gv = *reinterpret_cast<const dolg_f32x4*>(g + i);
-    const dolg_f32x4 mv = *reinterpret_cast<const dolg_f32x4*>(mr + i);
-    *reinterpret_cast<dolg_f32x4*>(o + i) = gv;
-    *reinterpret_cast<dolg_f32x4*>(o + c + i) = mv - gv * k;
-  }
-}
-
-// The partial slabs of a split image live in a buffer the handle owns, one per
-// stream (launches on one stream are ordered, so they may share it; two
-// streams never do).  It grows on demand; the old buffer is freed only after
-// its stream has drained.
-struct DolgSlabs {
-  std::mutex mu;
-  std::map<std::pair<rr_handle_s*, hipStream_t>, std::pair<float*, size_t>> bufs;
-};
-static DolgSlabs& dolg_slabs() {
-  static DolgSlabs* s = new DolgSlabs();  // never destroyed: no HIP call at process exit
-  return *s;
-}
-
-static int dolg_slab_get(rr_handle_s* h, hipStream_t s, size_t bytes, float** out) {
-  DolgSlabs& ds = dolg_slabs();
-  std::lock_guard<std::mutex> lk(ds.mu);
-  auto& e = ds.bufs[{h, s}];
-  if (e.second < bytes) {
-    if (e.first) {
-      if (int rc = check_hip(h, hipStreamSynchronize(s), "dolg slab sync")) return rc;
-      (void)hipFree(e.first);
-      e = {nullptr, 0};
-    }
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) return set_error(h, RR_EWORKSPACE, "rr_dolg_local_pool: cannot allocate the partial slabs");
-    e = {(float*)p, bytes};
-  }
-  *out = e.first;
-  return RR_OK;
-}
-
-void dolg_slab_release(rr_handle_s* h) {
-  DolgSlabs& ds = dolg_slabs();
-  std::lock_guard<std::mutex> lk(ds.mu);
-  for (auto it = ds.bufs.begin(); it != ds.bufs.end();) {
-    if (it->first.first == h) {
-      if (it->second.first) (void)hipFree(it->second.first);
-      it = ds.bufs.erase(it);
-    } else {
-      ++it;
-    }
+    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i);
+    const f32x4 mv = *reinterpret_cast<const f32x4*>(mr + i);
+    *reinterpret_cast<f32x4*>(o + i) = gv;
+    *reinterpret_cast<f32x4*>(o + c + i) = mv - gv * k;
   }
 }
 
@@ -220,22 +147,16 @@ extern "C" int rr_dolg_local_pool(rr_handle_t h, const float* y, int b, int hw, 
       ((uintptr_t)out & 15) || ((uintptr_t)w2 & 15))
     return set_error(h, RR_EINVAL, "rr_dolg_local_pool: bad argument (c % 256 == 0, c <= 2048, hw > 0, 16-B aligned)");
   if (b == 0) return RR_OK;
-  // an image's pixels are split over workgroups only while whole images leave
-  // the chip short of work; the split depends on (b, hw) alone
-  int splits = 1, chunk = hw;
-  if (b < kPoolTargetBlocks) {
-    const int want = (kPoolTargetBlocks + b - 1) / b;
-    const int most = (hw + kPoolMinPixels - 1) / kPoolMinPixels;
-    splits = want < most ? want : most;
-    chunk = (hw + splits - 1) / splits;
-    splits = (hw + chunk - 1) / chunk;
-  }
+  const auto [splits, chunk] = split_positions(b, hw, kPoolMinPixels, kPoolTargetBlocks);
   const long long blocks = (long long)b * splits;
   if (blocks > 0x7fffffffLL) return set_error(h, RR_EINVAL, "rr_dolg_local_pool: too many images");
   hipStream_t s = (hipStream_t)stream;
   float* dst = out;
-  if (splits > 1)
-    if (int rc = dolg_slab_get(h, s, (size_t)blocks * c * sizeof(float), &dst)) return rc;
+  if (splits > 1) {
+    void* p = nullptr;
+    if (int rc = stream_scratch(h, s, (size_t)blocks * c * sizeof(float), &p, "rr_dolg_local_pool")) return rc;
+    dst = (float*)p;
+  }
   TimedLaunch tl(h, kTimeElem, s);
   switch (c >> 8) {
     case 1: launch_pool<1>(y, hw, chunk, splits, w2, b2, dst, (unsigned)blocks, s); break;
@@ -248,11 +169,7 @@ extern "C" int rr_dolg_local_pool(rr_handle_t h, const float* y, int b, int hw, 
     default: launch_pool<8>(y, hw, chunk, splits, w2, b2, dst, (unsigned)blocks, s); break;
   }
   if (int rc = check_hip(h, hipGetLastError(), "dolg_local_pool launch")) return rc;
-  if (splits > 1) {
-    hipLaunchKernelGGL(dolg_pool_sum_kernel, dim3((unsigned)(b * (c >> 8))), dim3(kSumWaves * 64), 0, s, dst, splits, c,
-                       hw, out);
-    return check_hip(h, hipGetLastError(), "dolg_pool_sum launch");
-  }
+  if (splits > 1) return check_hip(h, launch_slab_sum<true>(dst, b, splits, c, hw, out, s), "dolg_pool_sum launch");
   return RR_OK;
 }
 

@@ -7,15 +7,10 @@
 // softmax(-alpha dist), the loop over the centroids) and ASMKPooling.forward
 // :80-99 (cdist, argmin, gather, mean + std threshold, the double loop).
 #include <cmath>
-#include <map>
-#include <mutex>
-#include <tuple>
 
-#include "rr_internal.hpp"
+#include "heads_common.hpp"
 
 namespace rr {
-
-typedef float how_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kHowWaves = 4;            // waves per workgroup (256 threads)
 constexpr int kHowThreads = kHowWaves * 64;
@@ -105,14 +100,14 @@ __global__ __launch_bounds__(kHowThreads) void how_pool_kernel(const float* __re
   const float* xi = x + (long long)img * n * d;
   const int prow = tid / TPP, psub = tid - prow * TPP;  // phases 0 and 2: the thread's row of the step
 
-  how_f32x4 xr[NV];
+  f32x4 xr[NV];
   auto load_step = [&](int st) {
     const int p = p0 + st * P + prow;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int f = psub + i * TPP;
-      xr[i] = how_f32x4{0.f, 0.f, 0.f, 0.f};
-      if (p < p1 && f < d4) xr[i] = *reinterpret_cast<const how_f32x4*>(xi + (long long)p * d + f * 4);
+      xr[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (p < p1 && f < d4) xr[i] = *reinterpret_cast<const f32x4*>(xi + (long long)p * d + f * 4);
     }
   };
   load_step(0);
@@ -121,9 +116,9 @@ __global__ __launch_bounds__(kHowThreads) void how_pool_kernel(const float* __re
   // added in one order: identical centroids get identical norms)
   for (int i = tid; i < KT * 16 * d4; i += kHowThreads) {
     const int row = i / d4, c4 = i - row * d4;
-    how_f32x4 v = how_f32x4{0.f, 0.f, 0.f, 0.f};
-    if (row < k) v = *reinterpret_cast<const how_f32x4*>(cent + (long long)row * d + c4 * 4);
-    *reinterpret_cast<how_f32x4*>(Cs + row * L.ldc + c4 * 4) = v;
+    f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (row < k) v = *reinterpret_cast<const f32x4*>(cent + (long long)row * d + c4 * 4);
+    *reinterpret_cast<f32x4*>(Cs + row * L.ldc + c4 * 4) = v;
   }
   __syncthreads();
   {
@@ -138,13 +133,13 @@ __global__ __launch_bounds__(kHowThreads) void how_pool_kernel(const float* __re
     if (c < KT * 16 && half == 0) cn[c] = s;
   }
 
-  how_f32x4 acc[KTMAX][NJ];
+  f32x4 acc[KTMAX][NJ];
   float psum[KTMAX];
 #pragma unroll
   for (int kt = 0; kt < KTMAX; ++kt) {
     psum[kt] = 0.f;
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[kt][j] = how_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NJ; ++j) acc[kt][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
   for (int st = 0; st < steps; ++st) {
@@ -162,13 +157,13 @@ __global__ __launch_bounds__(kHowThreads) void how_pool_kernel(const float* __re
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
         const int f = psub + i * TPP;
-        how_f32x4 v;
+        f32x4 v;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           v[e] = xr[i][e] / den;
           s2 = fmaf(v[e], v[e], s2);
         }
-        if (f < d4) *reinterpret_cast<how_f32x4*>(Xs + prow * L.ldc + f * 4) = v;
+        if (f < d4) *reinterpret_cast<f32x4*>(Xs + prow * L.ldc + f * 4) = v;
       }
       s2 = how_group_sum(s2, TPP);
       if (psub == 0) xn[prow] = s2;
@@ -183,19 +178,19 @@ __global__ __launch_bounds__(kHowThreads) void how_pool_kernel(const float* __re
       for (int i = 0; i < (KTMAX * NPT + kHowWaves - 1) / kHowWaves; ++i) {
         const int kt = wave / NPT + i * (kHowWaves / NPT);
         if (kt < KT) {  // wave-uniform
-          how_f32x4 a4[4];
+          f32x4 a4[4];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) a4[e] = how_f32x4{0.f, 0.f, 0.f, 0.f};
+          for (int e = 0; e < 4; ++e) a4[e] = f32x4{0.f, 0.f, 0.f, 0.f};
           const float* cp = Cs + (16 * kt + lq) * L.ldc + 4 * lg;
           const float* xp = Xs + (16 * pt + lq) * L.ldc + 4 * lg;
           for (int j = 0; j < DT; ++j) {
-            const how_f32x4 cf = *reinterpret_cast<const how_f32x4*>(cp + 16 * j);
-            const how_f32x4 xf = *reinterpret_cast<const how_f32x4*>(xp + 16 * j);
+            const f32x4 cf = *reinterpret_cast<const f32x4*>(cp + 16 * j);
+            const f32x4 xf = *reinterpret_cast<const f32x4*>(xp + 16 * j);
 #pragma unroll
             for (int e = 0; e < 4; ++e) a4[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(cf[e], xf[e], a4[e], 0, 0, 0);
           }
-          const how_f32x4 s = (a4[0] + a4[1]) + (a4[2] + a4[3]);
-          *reinterpret_cast<how_f32x4*>(As + (16 * pt + lq) * L.lda + 16 * kt + 4 * lg) = s;
+          const f32x4 s = (a4[0] + a4[1]) + (a4[2] + a4[3]);
+          *reinterpret_cast<f32x4*>(As + (16 * pt + lq) * L.lda + 16 * kt + 4 * lg) = s;
         }
       }
     }
@@ -324,10 +319,10 @@ __global__ __launch_bounds__(256) void how_sum_kernel(const float* __restrict__ 
   const long long img = i / len4;
   const int g = (int)(i - img * len4);
   const float* pp = part + (img * splits * len4 + g) * 4;
-  how_f32x4 t = how_f32x4{0.f, 0.f, 0.f, 0.f};
+  f32x4 t = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 8
-  for (int s = 0; s < splits; ++s) t += *reinterpret_cast<const how_f32x4*>(pp + (long long)s * len4 * 4);
-  *reinterpret_cast<how_f32x4*>(out + i * 4) = t;
+  for (int s = 0; s < splits; ++s) t += *reinterpret_cast<const f32x4*>(pp + (long long)s * len4 * 4);
+  *reinterpret_cast<f32x4*>(out + i * 4) = t;
 }
 
 // ASMK's second pass, one workgroup per image over its n (smallest distance,
@@ -369,66 +364,13 @@ __global__ __launch_bounds__(256) void how_asmk_count_kernel(const float* __rest
   if (tid < k) out[(long long)blockIdx.x * k + tid] = w[tid] * (float)cnt[tid];
 }
 
-// The partial slabs of a split image (VLAD) and the per-position minima (ASMK)
-// live in a buffer kept per (handle, device, stream), as rr_token_pool's:
-// launches on one stream are ordered, so they may share it; two streams never
-// do.  It grows on demand (the old buffer is freed only after its stream has
-// drained) and is kept until the process ends.
-struct HowSlabs {
-  std::mutex mu;
-  std::map<std::tuple<rr_handle_s*, int, hipStream_t>, std::pair<void*, size_t>> bufs;
-};
-static HowSlabs& how_slabs() {
-  static HowSlabs* s = new HowSlabs();  // never destroyed: no HIP call at process exit
-  return *s;
-}
-
-static int how_slab_get(rr_handle_s* h, hipStream_t s, size_t bytes, void** out, const char* who) {
-  HowSlabs& hs = how_slabs();
-  std::lock_guard<std::mutex> lk(hs.mu);
-  auto& e = hs.bufs[std::make_tuple(h, h->device, s)];
-  if (e.second < bytes) {
-    if (e.first) {
-      if (int rc = check_hip(h, hipStreamSynchronize(s), "how slab sync")) return rc;
-      (void)hipFree(e.first);
-      e = {nullptr, 0};
-    }
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess)
-      return set_error(h, RR_EWORKSPACE, std::string(who) + ": cannot allocate the workspace");
-    e = {p, bytes};
-  }
-  *out = e.first;
-  return RR_OK;
-}
-
-// an image's positions are split over workgroups only while whole images leave
-// the chip short of work; the split depends on (b, n) alone
-static void how_split(int b, int n, int* splits, int* chunk) {
-  *splits = 1;
-  *chunk = n;
-  if (b < kHowTargetBlocks) {
-    const int want = (kHowTargetBlocks + b - 1) / b;
-    const int most = (n + kHowMinPos - 1) / kHowMinPos;
-    const int sp = want < most ? want : most;
-    *chunk = (n + sp - 1) / sp;
-    *splits = (n + *chunk - 1) / *chunk;
-  }
-}
-
 template <int KTMAX, int NJ, bool ASMK>
 static hipError_t launch_how_pool(const float* x, int n, int d, int chunk, int splits, const float* cent, int k,
                                   float alpha, float* dst, int* dst_idx, unsigned blocks, hipStream_t s) {
   constexpr int P = (KTMAX == 8 && NJ == 4) ? 16 : 32;
   const size_t lds = (size_t)HowLds(((k + 15) >> 4) * 16, d, P).total * sizeof(float);
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)how_pool_kernel<KTMAX, NJ, ASMK>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((how_pool_kernel<KTMAX, NJ, ASMK>), dim3(blocks), dim3(kHowThreads), lds, s, x, n, d, chunk, splits,
-                     cent, k, alpha, dst, dst_idx);
-  return hipGetLastError();
+  return launch_dyn_lds(how_pool_kernel<KTMAX, NJ, ASMK>, blocks, kHowThreads, lds, s, x, n, d, chunk, splits, cent, k,
+                        alpha, dst, dst_idx);
 }
 
 template <bool ASMK>
@@ -458,8 +400,7 @@ extern "C" int rr_how_vlad(rr_handle_t h, const float* x, int b, int n, int d, c
                      "rr_how_vlad: bad argument (1 <= k <= 128, d % 32 == 0, 32 <= d <= 256, 1 <= n <= 65535, 16-B "
                      "aligned)");
   if (b == 0) return RR_OK;
-  int splits, chunk;
-  how_split(b, n, &splits, &chunk);
+  const auto [splits, chunk] = split_positions(b, n, kHowMinPos, kHowTargetBlocks);
   const long long blocks = (long long)b * splits;
   const long long len = (long long)k * d;
   const long long total4 = (long long)b * (len >> 2);
@@ -469,7 +410,7 @@ extern "C" int rr_how_vlad(rr_handle_t h, const float* x, int b, int n, int d, c
   float* dst = out;
   if (splits > 1) {
     void* p = nullptr;
-    if (int rc = how_slab_get(h, s, (size_t)blocks * len * sizeof(float), &p, "rr_how_vlad")) return rc;
+    if (int rc = stream_scratch(h, s, (size_t)blocks * len * sizeof(float), &p, "rr_how_vlad")) return rc;
     dst = (float*)p;
   }
   TimedLaunch tl(h, kTimeElem, s);
@@ -494,15 +435,14 @@ extern "C" int rr_how_asmk(rr_handle_t h, const float* x, int b, int n, int d, c
                      "rr_how_asmk: bad argument (1 <= k <= 128, d % 32 == 0, 32 <= d <= 256, 1 <= n <= 65535, 16-B "
                      "aligned)");
   if (b == 0) return RR_OK;
-  int splits, chunk;
-  how_split(b, n, &splits, &chunk);
+  const auto [splits, chunk] = split_positions(b, n, kHowMinPos, kHowTargetBlocks);
   const long long blocks = (long long)b * splits;
   if (blocks > 0x7fffffffLL) return set_error(h, RR_EINVAL, "rr_how_asmk: too many images");
   hipStream_t s = (hipStream_t)stream;
   // [b n] smallest distances, then [b n] centroid indices
   const size_t cells = (size_t)b * n;
   void* p = nullptr;
-  if (int rc = how_slab_get(h, s, cells * (sizeof(float) + sizeof(int)), &p, "rr_how_asmk")) return rc;
+  if (int rc = stream_scratch(h, s, cells * (sizeof(float) + sizeof(int)), &p, "rr_how_asmk")) return rc;
   float* minv = (float*)p;
   int* mini = (int*)(minv + cells);
   TimedLaunch tl(h, kTimeElem, s);

@@ -100,7 +100,8 @@ int rr_destroy(rr_handle_t h) {
       (void)hipEventDestroy(h->ev_start[c][i]);
       (void)hipEventDestroy(h->ev_stop[c][i]);
     }
-  dolg_slab_release(h);
+  for (auto& e : h->scratch)
+    if (e.second.first) (void)hipFree(e.second.first);
   delete h;
   return RR_OK;
 }

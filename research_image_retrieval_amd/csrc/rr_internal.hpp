@@ -4,8 +4,10 @@
 #include <type_traits>
 
 #include <hip/hip_runtime.h>
+#include <map>
 #include <stdint.h>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/rr.h"
@@ -41,6 +43,9 @@ struct rr_handle_s {
   int n_ev[kClasses] = {};
   double acc_ms[kClasses] = {};
   long long acc_launches[kClasses] = {};
+  // the extractor heads' per-stream scratch (heads_common.hpp: stream_scratch);
+  // rr_destroy frees it
+  std::map<hipStream_t, std::pair<void*, size_t>> scratch;
 };
 
 namespace rr {
@@ -349,8 +354,5 @@ bool lpp_eligible(const GemmArgs& g);
 hipError_t launch_lpp(const GemmArgs& g, hipStream_t s, int n_cu);
 bool lpp3_eligible(const GemmArgs& g);
 hipError_t launch_lpp3(const GemmArgs& g, hipStream_t s, int n_cu);
-
-// dolg_ops.hip: frees the partial-slab buffers rr_dolg_local_pool keeps for h
-void dolg_slab_release(rr_handle_s* h);
 
 }  // namespace rr

@@ -9,11 +9,9 @@
 // (online softmax), both products on the exact-fp32 MFMA.
 #include <cmath>
 
-#include "rr_internal.hpp"
+#include "heads_common.hpp"
 
 namespace rr {
-
-typedef float soa_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kSoaTile = 16;  // queries per workgroup = keys per streamed tile
 constexpr int kSoaWaves = 4;  // waves per workgroup; wave w owns channels [w c/4, (w + 1) c/4)
@@ -37,11 +35,7 @@ constexpr size_t soa_lds_bytes(int c) {
 //   the chain and are added in a fixed order.
 //  the four waves' partial tiles are added through LDS in wave order; every
 //   wave then does the same softmax step for all 16 queries (same operations,
-//   same bits): scale, mask keys >= hw to -inf, tile max and sum over the
-//   lane's 4 keys and the 3 partner lanes (xor 16, 32), running max m and sum l.
-//   m starts at -inf and the tile max is finite (a tile's first key is < hw),
-//   so alpha = exp(m - m_new) is exp(-inf) = 0 on the first tile, never
-//   (-inf) - (-inf).
+//   same bits): online_softmax_step (a tile's first key is < hw).
 //  O^T += h^T . P^T over the wave's own 256 NV / 4 output channels: A = the h
 //   tile read at [key 4 lg + r][channel lq] (row = channel), B = p[r] as it
 //   sits in the lane (k = key 4 lg + r, col = query lq): no lane movement.
@@ -64,16 +58,16 @@ __global__ __launch_bounds__(kSoaWaves * 64) void soa_attention_kernel(const flo
   const int q = qt * kSoaTile + lq;
   const int c0 = wave * CS;
 
-  soa_f32x4 qf[NJ], o[NJ];
+  f32x4 qf[NJ], o[NJ];
   {
     const bool ok = q < hw;  // a query past the map computes on zeros and is not stored
     const float* qp = base + (long long)(ok ? q : 0) * (3 * C) + c0 + 4 * lg;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      soa_f32x4 v = *reinterpret_cast<const soa_f32x4*>(qp + 16 * j);
+      f32x4 v = *reinterpret_cast<const f32x4*>(qp + 16 * j);
 #pragma unroll
       for (int e = 0; e < 4; ++e) qf[j][e] = ok ? fmaxf(v[e], 0.f) : 0.f;
-      o[j] = soa_f32x4{0.f, 0.f, 0.f, 0.f};
+      o[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
   }
   float m = -__builtin_inff(), l = 0.f;
@@ -83,18 +77,18 @@ __global__ __launch_bounds__(kSoaWaves * 64) void soa_attention_kernel(const flo
   // next tile's loads are issued before this tile's arithmetic and waited
   // for only at the next store, so their latency hides under the MFMAs.
   constexpr int NI = kSoaTile * G4 / (kSoaWaves * 64);
-  soa_f32x4 gv[NI], hv[NI];
+  f32x4 gv[NI], hv[NI];
   auto load_tile = [&](int kt) {
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int idx = tid + i * (kSoaWaves * 64);
       const int row = idx / G4, c4 = idx - row * G4;
       const int key = kt * kSoaTile + row;
-      gv[i] = hv[i] = soa_f32x4{0.f, 0.f, 0.f, 0.f};
+      gv[i] = hv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (key < hw) {
         const float* p = base + (long long)key * (3 * C) + c4 * 4;
-        gv[i] = *reinterpret_cast<const soa_f32x4*>(p + C);
-        hv[i] = *reinterpret_cast<const soa_f32x4*>(p + 2 * C);
+        gv[i] = *reinterpret_cast<const f32x4*>(p + C);
+        hv[i] = *reinterpret_cast<const f32x4*>(p + 2 * C);
       }
     }
   };
@@ -105,49 +99,36 @@ __global__ __launch_bounds__(kSoaWaves * 64) void soa_attention_kernel(const flo
     for (int i = 0; i < NI; ++i) {
       const int idx = tid + i * (kSoaWaves * 64);
       const int row = idx / G4, c4 = idx - row * G4;
-      soa_f32x4 gr;
+      f32x4 gr;
 #pragma unroll
       for (int e = 0; e < 4; ++e) gr[e] = fmaxf(gv[i][e], 0.f);
-      *reinterpret_cast<soa_f32x4*>(Gs + row * LD + c4 * 4) = gr;
-      *reinterpret_cast<soa_f32x4*>(Hs + row * LD + c4 * 4) = hv[i];
+      *reinterpret_cast<f32x4*>(Gs + row * LD + c4 * 4) = gr;
+      *reinterpret_cast<f32x4*>(Hs + row * LD + c4 * 4) = hv[i];
     }
     if (kt + 1 < ntiles) load_tile(kt + 1);
     __syncthreads();
 
-    soa_f32x4 acc[4];
+    f32x4 acc[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] = soa_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int e = 0; e < 4; ++e) acc[e] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      const soa_f32x4 kf = *reinterpret_cast<const soa_f32x4*>(Gs + lq * LD + c0 + 16 * j + 4 * lg);
+      const f32x4 kf = *reinterpret_cast<const f32x4*>(Gs + lq * LD + c0 + 16 * j + 4 * lg);
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[e], qf[j][e], acc[e], 0, 0, 0);
     }
-    *reinterpret_cast<soa_f32x4*>(Sp + wave * (kSoaTile * kSoaTile) + lq * kSoaTile + 4 * lg) =
+    *reinterpret_cast<f32x4*>(Sp + wave * (kSoaTile * kSoaTile) + lq * kSoaTile + 4 * lg) =
         (acc[0] + acc[1]) + (acc[2] + acc[3]);
     __syncthreads();
 
     const float* sp = Sp + lq * kSoaTile + 4 * lg;
-    soa_f32x4 s = (*reinterpret_cast<const soa_f32x4*>(sp) + *reinterpret_cast<const soa_f32x4*>(sp + 256)) +
-                  (*reinterpret_cast<const soa_f32x4*>(sp + 512) + *reinterpret_cast<const soa_f32x4*>(sp + 768));
-    float tmax = -__builtin_inff();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      s[r] = kt * kSoaTile + 4 * lg + r < hw ? s[r] * scale : -__builtin_inff();
-      tmax = fmaxf(tmax, s[r]);
-    }
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    const float mn = fmaxf(m, tmax);
-    const float alpha = expf(m - mn);
-    soa_f32x4 p;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) p[r] = expf(s[r] - mn);
-    float ps = (p[0] + p[1]) + (p[2] + p[3]);
-    ps += __shfl_xor(ps, 16, 64);
-    ps += __shfl_xor(ps, 32, 64);
-    l = l * alpha + ps;
-    m = mn;
+    const f32x4 s = (*reinterpret_cast<const f32x4*>(sp) + *reinterpret_cast<const f32x4*>(sp + 256)) +
+                    (*reinterpret_cast<const f32x4*>(sp + 512) + *reinterpret_cast<const f32x4*>(sp + 768));
+    const SoftmaxTile st = online_softmax_step(s, kt * kSoaTile, hw, scale, lg, m, l);
+    const f32x4 p = st.p;
+    const float alpha = st.alpha;
+    l = st.l;
+    m = st.m;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       o[j] *= alpha;
@@ -159,21 +140,15 @@ __global__ __launch_bounds__(kSoaWaves * 64) void soa_attention_kernel(const flo
   if (q < hw) {
     float* op = out + ((long long)img * hw + q) * C + c0 + 4 * lg;
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) *reinterpret_cast<soa_f32x4*>(op + 16 * j) = o[j] / l;
+    for (int j = 0; j < NJ; ++j) *reinterpret_cast<f32x4*>(op + 16 * j) = o[j] / l;
   }
 }
 
 template <int NV>
 static hipError_t launch_soa(const float* fgh, int hw, int qtiles, float scale, float* out, unsigned blocks,
                              hipStream_t s) {
-  const size_t lds = soa_lds_bytes(NV * 256);
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)soa_attention_kernel<NV>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(soa_attention_kernel<NV>, dim3(blocks), dim3(kSoaWaves * 64), lds, s, fgh, hw, qtiles, scale, out);
-  return hipGetLastError();
+  return launch_dyn_lds(soa_attention_kernel<NV>, blocks, kSoaWaves * 64, soa_lds_bytes(NV * 256), s, fgh, hw, qtiles,
+                        scale, out);
 }
 
 }  // namespace rr

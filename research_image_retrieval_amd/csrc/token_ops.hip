@@ -8,15 +8,10 @@
 // over the tokens), Token_Refine.forward :180-182 (softmax over the objects,
 // attns @ x) and GELU :67-72 (F.gelu, the erf form).
 #include <cmath>
-#include <map>
-#include <mutex>
-#include <tuple>
 
-#include "rr_internal.hpp"
+#include "heads_common.hpp"
 
 namespace rr {
-
-typedef float tok_f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- rr_attention_hd128 ---------------------------------------------------
 constexpr int kHdDim = 128;        // head width
@@ -40,11 +35,8 @@ constexpr int kHdWaves = 4;
 //   channels), B = the wave's Q fragments (registers, loaded once); four
 //   accumulators, one per 4-channel phase, added in a fixed order.  Lane
 //   (lq, lg) ends with S[query lq][key 4 lg + reg].
-//  softmax step: scale, keys >= nk to -inf, tile max and sum over the lane's 4
-//   keys and its partner lanes (xor 16, 32), running max m and sum l.  m starts
-//   at -inf; a wave only enters a tile whose first key is < nk, so the tile
-//   max is finite and alpha = exp(m - m_new) is exp(-inf) = 0 on the first
-//   tile, never (-inf) - (-inf).
+//  softmax step: online_softmax_step (a wave only enters a tile whose first
+//   key is < nk).
 //  O^T += V^T . P^T: A = the V tile read at [key 4 lg + r][channel 16 j + lq],
 //   B = p[r] as it sits in the lane; D: lane (lq, lg) holds O[query lq]
 //   [channel 16 j + 4 lg + reg].
@@ -67,14 +59,14 @@ __global__ __launch_bounds__(kHdWaves * 64) void attention_hd128_kernel(
   const int qi = q0 + lq;
   const bool qok = qi < nq;  // a query past nq computes on zeros and is not stored
 
-  tok_f32x4 qf[NJ], o[NJ];
+  f32x4 qf[NJ], o[NJ];
   {
     const float* qp = q + ((long long)img * nq + (qok ? qi : 0)) * ldq + head * kHdDim + 4 * lg;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      const tok_f32x4 t = *reinterpret_cast<const tok_f32x4*>(qp + 16 * j);
-      qf[j] = qok ? t : tok_f32x4{0.f, 0.f, 0.f, 0.f};
-      o[j] = tok_f32x4{0.f, 0.f, 0.f, 0.f};
+      const f32x4 t = *reinterpret_cast<const f32x4*>(qp + 16 * j);
+      qf[j] = qok ? t : f32x4{0.f, 0.f, 0.f, 0.f};
+      o[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
   }
   float m = -__builtin_inff(), l = 0.f;
@@ -84,17 +76,17 @@ __global__ __launch_bounds__(kHdWaves * 64) void attention_hd128_kernel(
   // A tile's K and V rows (zero past nk) travel global -> registers -> LDS,
   // thread t taking 16-B group t + 256 i of the tile's R x 32; the next tile's
   // loads are issued before this tile's arithmetic.
-  tok_f32x4 kv[NI], vv[NI];
+  f32x4 kv[NI], vv[NI];
   auto load_tile = [&](int kt) {
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int idx = tid + i * (kHdWaves * 64);
       const int row = idx >> 5, c4 = idx & 31;
       const int key = kt * R + row;
-      kv[i] = vv[i] = tok_f32x4{0.f, 0.f, 0.f, 0.f};
+      kv[i] = vv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (key < nk) {
-        kv[i] = *reinterpret_cast<const tok_f32x4*>(kb + (long long)key * ldk + c4 * 4);
-        vv[i] = *reinterpret_cast<const tok_f32x4*>(vb + (long long)key * ldv + c4 * 4);
+        kv[i] = *reinterpret_cast<const f32x4*>(kb + (long long)key * ldk + c4 * 4);
+        vv[i] = *reinterpret_cast<const f32x4*>(vb + (long long)key * ldv + c4 * 4);
       }
     }
   };
@@ -105,8 +97,8 @@ __global__ __launch_bounds__(kHdWaves * 64) void attention_hd128_kernel(
     for (int i = 0; i < NI; ++i) {
       const int idx = tid + i * (kHdWaves * 64);
       const int row = idx >> 5, c4 = idx & 31;
-      *reinterpret_cast<tok_f32x4*>(Ks + row * kHdLd + c4 * 4) = kv[i];
-      *reinterpret_cast<tok_f32x4*>(Vs + row * kHdLd + c4 * 4) = vv[i];
+      *reinterpret_cast<f32x4*>(Ks + row * kHdLd + c4 * 4) = kv[i];
+      *reinterpret_cast<f32x4*>(Vs + row * kHdLd + c4 * 4) = vv[i];
     }
     if (kt + 1 < ntiles) load_tile(kt + 1);
     __syncthreads();
@@ -117,34 +109,20 @@ __global__ __launch_bounds__(kHdWaves * 64) void attention_hd128_kernel(
     const float* Kw = Ks + r0 * kHdLd;
     const float* Vw = Vs + r0 * kHdLd;
 
-    tok_f32x4 acc[4];
+    f32x4 acc[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] = tok_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int e = 0; e < 4; ++e) acc[e] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      const tok_f32x4 kf = *reinterpret_cast<const tok_f32x4*>(Kw + lq * kHdLd + 16 * j + 4 * lg);
+      const f32x4 kf = *reinterpret_cast<const f32x4*>(Kw + lq * kHdLd + 16 * j + 4 * lg);
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[e], qf[j][e], acc[e], 0, 0, 0);
     }
-    tok_f32x4 s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-    float tmax = -__builtin_inff();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      s[r] = key0 + 4 * lg + r < nk ? s[r] * scale : -__builtin_inff();
-      tmax = fmaxf(tmax, s[r]);
-    }
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    const float mn = fmaxf(m, tmax);
-    const float alpha = expf(m - mn);
-    tok_f32x4 p;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) p[r] = expf(s[r] - mn);
-    float ps = (p[0] + p[1]) + (p[2] + p[3]);
-    ps += __shfl_xor(ps, 16, 64);
-    ps += __shfl_xor(ps, 32, 64);
-    l = l * alpha + ps;
-    m = mn;
+    const SoftmaxTile st = online_softmax_step((acc[0] + acc[1]) + (acc[2] + acc[3]), key0, nk, scale, lg, m, l);
+    const f32x4 p = st.p;
+    const float alpha = st.alpha;
+    l = st.l;
+    m = st.m;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       o[j] *= alpha;
@@ -165,7 +143,7 @@ __global__ __launch_bounds__(kHdWaves * 64) void attention_hd128_kernel(
       Ml[((wave - 1) * 2 + 0) * 64 + lane] = m;
       Ml[((wave - 1) * 2 + 1) * 64 + lane] = l;
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) *reinterpret_cast<tok_f32x4*>(Ol + (((wave - 1) * NJ + j) * 64 + lane) * 4) = o[j];
+      for (int j = 0; j < NJ; ++j) *reinterpret_cast<f32x4*>(Ol + (((wave - 1) * NJ + j) * 64 + lane) * 4) = o[j];
     }
     __syncthreads();
     if (wave > 0) return;
@@ -181,13 +159,13 @@ __global__ __launch_bounds__(kHdWaves * 64) void attention_hd128_kernel(
       const float fw = expf(Ml[(w * 2 + 0) * 64 + lane] - M);
       l += Ml[(w * 2 + 1) * 64 + lane] * fw;
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) o[j] += *reinterpret_cast<const tok_f32x4*>(Ol + ((w * NJ + j) * 64 + lane) * 4) * fw;
+      for (int j = 0; j < NJ; ++j) o[j] += *reinterpret_cast<const f32x4*>(Ol + ((w * NJ + j) * 64 + lane) * 4) * fw;
     }
   }
   if (qok) {
     float* op = out + ((long long)img * nq + qi) * ((long long)heads * kHdDim) + head * kHdDim + 4 * lg;
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) *reinterpret_cast<tok_f32x4*>(op + 16 * j) = o[j] / l;
+    for (int j = 0; j < NJ; ++j) *reinterpret_cast<f32x4*>(op + 16 * j) = o[j] / l;
   }
 }
 
@@ -196,14 +174,8 @@ static hipError_t launch_hd128(const float* q, long long ldq, const float* k, lo
                                long long ldv, int nq, int nk, int heads, int qblocks, float scale, float* out,
                                unsigned blocks, hipStream_t s) {
   const size_t lds = (size_t)2 * (KSPLIT ? 64 : 16) * kHdLd * sizeof(float);
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)attention_hd128_kernel<KSPLIT>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(attention_hd128_kernel<KSPLIT>, dim3(blocks), dim3(kHdWaves * 64), lds, s, q, ldq, k, ldk, v, ldv, nq,
-                     nk, heads, qblocks, scale, out);
-  return hipGetLastError();
+  return launch_dyn_lds(attention_hd128_kernel<KSPLIT>, blocks, kHdWaves * 64, lds, s, q, ldq, k, ldk, v, ldv, nq, nk,
+                        heads, qblocks, scale, out);
 }
 
 // ---- rr_token_pool --------------------------------------------------------
@@ -220,7 +192,8 @@ constexpr int kTokTargetBlocks = 1024;  // workgroups wanted before images stop 
 // blockIdx.x = image * splits + s takes positions [s chunk, (s + 1) chunk),
 // wave w of it every kTokWaves-th position; the waves' accumulators are added
 // through LDS in wave order.  splits == 1: dst is out[image]; otherwise
-// part[image][s], which token_pool_sum_kernel adds in a fixed order.
+// part[image][s] (at most kTokTargetBlocks slabs of n_obj c floats, 32 MiB),
+// which slab_sum_kernel<false> adds in a fixed order.
 template <int NV>
 __global__ __launch_bounds__(kTokWaves * 64) void token_pool_kernel(const float* __restrict__ x, int hw, int chunk,
                                                                     int splits, const float* __restrict__ query,
@@ -234,26 +207,26 @@ __global__ __launch_bounds__(kTokWaves * 64) void token_pool_kernel(const float*
   const float* xi = x + (long long)img * hw * C + lane * 4;
 
   for (int i = tid; i < n_obj * (C / 4); i += kTokWaves * 64)
-    *reinterpret_cast<tok_f32x4*>(tok_lds + i * 4) = *reinterpret_cast<const tok_f32x4*>(query + i * 4);
+    *reinterpret_cast<f32x4*>(tok_lds + i * 4) = *reinterpret_cast<const f32x4*>(query + i * 4);
   __syncthreads();
 
-  tok_f32x4 acc[kTokMaxObj][NV], cur[NV], nxt[NV];
+  f32x4 acc[kTokMaxObj][NV], cur[NV], nxt[NV];
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
-    cur[j] = nxt[j] = tok_f32x4{0.f, 0.f, 0.f, 0.f};
+    cur[j] = nxt[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int ob = 0; ob < kTokMaxObj; ++ob) acc[ob][j] = tok_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int ob = 0; ob < kTokMaxObj; ++ob) acc[ob][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   int p = p0 + wave;  // wave-uniform
   if (p < p1) {
 #pragma unroll
-    for (int j = 0; j < NV; ++j) cur[j] = *reinterpret_cast<const tok_f32x4*>(xi + (long long)p * C + j * 256);
+    for (int j = 0; j < NV; ++j) cur[j] = *reinterpret_cast<const f32x4*>(xi + (long long)p * C + j * 256);
   }
   for (; p < p1; p += kTokWaves) {
     const int pn = p + kTokWaves;
     if (pn < p1) {  // the next row's loads fly under this row's arithmetic
 #pragma unroll
-      for (int j = 0; j < NV; ++j) nxt[j] = *reinterpret_cast<const tok_f32x4*>(xi + (long long)pn * C + j * 256);
+      for (int j = 0; j < NV; ++j) nxt[j] = *reinterpret_cast<const f32x4*>(xi + (long long)pn * C + j * 256);
     }
     float lg[kTokMaxObj];
     float mx = -__builtin_inff();
@@ -264,7 +237,7 @@ __global__ __launch_bounds__(kTokWaves * 64) void token_pool_kernel(const float*
         float d = 0.f;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
-          const tok_f32x4 qv = *reinterpret_cast<const tok_f32x4*>(tok_lds + ob * C + j * 256 + lane * 4);
+          const f32x4 qv = *reinterpret_cast<const f32x4*>(tok_lds + ob * C + j * 256 + lane * 4);
 #pragma unroll
           for (int e = 0; e < 4; ++e) d = fmaf(qv[e], cur[j][e], d);
         }
@@ -298,7 +271,7 @@ __global__ __launch_bounds__(kTokWaves * 64) void token_pool_kernel(const float*
       for (int ob = 0; ob < kTokMaxObj; ++ob)
         if (ob < n_obj) {
 #pragma unroll
-          for (int j = 0; j < NV; ++j) *reinterpret_cast<tok_f32x4*>(tok_lds + ob * C + j * 256 + lane * 4) = acc[ob][j];
+          for (int j = 0; j < NV; ++j) *reinterpret_cast<f32x4*>(tok_lds + ob * C + j * 256 + lane * 4) = acc[ob][j];
         }
     }
     __syncthreads();
@@ -308,7 +281,7 @@ __global__ __launch_bounds__(kTokWaves * 64) void token_pool_kernel(const float*
         if (ob < n_obj) {
 #pragma unroll
           for (int j = 0; j < NV; ++j)
-            acc[ob][j] += *reinterpret_cast<const tok_f32x4*>(tok_lds + ob * C + j * 256 + lane * 4);
+            acc[ob][j] += *reinterpret_cast<const f32x4*>(tok_lds + ob * C + j * 256 + lane * 4);
         }
     }
   }
@@ -318,64 +291,9 @@ __global__ __launch_bounds__(kTokWaves * 64) void token_pool_kernel(const float*
     for (int ob = 0; ob < kTokMaxObj; ++ob)
       if (ob < n_obj) {
 #pragma unroll
-        for (int j = 0; j < NV; ++j) *reinterpret_cast<tok_f32x4*>(o + ob * C + j * 256) = acc[ob][j];
+        for (int j = 0; j < NV; ++j) *reinterpret_cast<f32x4*>(o + ob * C + j * 256) = acc[ob][j];
       }
   }
-}
-
-// out[img][:] = sum_s part[img][s][:] over rows of len = n_obj c floats in a
-// fixed order: workgroup (image, 256-float group), wave w adds slabs w, w + 16,
-// ... in that order, then the waves' sums are added through LDS in wave order.
-constexpr int kTokSumWaves = 16;
-__global__ __launch_bounds__(kTokSumWaves * 64) void token_pool_sum_kernel(const float* __restrict__ part, int splits,
-                                                                           int len, float* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) float red[(kTokSumWaves - 1) * 256];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int groups = len >> 8;
-  const int img = blockIdx.x / groups, g = blockIdx.x - img * groups;
-  const float* pp = part + (long long)img * splits * len + g * 256 + lane * 4;
-  tok_f32x4 t = tok_f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-  for (int s = wave; s < splits; s += kTokSumWaves) t += *reinterpret_cast<const tok_f32x4*>(pp + (long long)s * len);
-  if (wave > 0) *reinterpret_cast<tok_f32x4*>(red + (wave - 1) * 256 + lane * 4) = t;
-  __syncthreads();
-  if (wave == 0) {
-#pragma unroll
-    for (int w = 0; w < kTokSumWaves - 1; ++w) t += *reinterpret_cast<const tok_f32x4*>(red + w * 256 + lane * 4);
-    *reinterpret_cast<tok_f32x4*>(out + (long long)img * len + g * 256 + lane * 4) = t;
-  }
-}
-
-// The partial slabs of a split image live in a buffer kept per (handle, device,
-// stream), as rr_dolg_local_pool's: launches on one stream are ordered, so they
-// may share it; two streams never do.  It grows on demand (the old buffer is
-// freed only after its stream has drained) and is at most kTokTargetBlocks
-// slabs of n_obj c floats (32 MiB).  It is kept until the process ends.
-struct TokSlabs {
-  std::mutex mu;
-  std::map<std::tuple<rr_handle_s*, int, hipStream_t>, std::pair<float*, size_t>> bufs;
-};
-static TokSlabs& tok_slabs() {
-  static TokSlabs* s = new TokSlabs();  // never destroyed: no HIP call at process exit
-  return *s;
-}
-
-static int tok_slab_get(rr_handle_s* h, hipStream_t s, size_t bytes, float** out) {
-  TokSlabs& ts = tok_slabs();
-  std::lock_guard<std::mutex> lk(ts.mu);
-  auto& e = ts.bufs[std::make_tuple(h, h->device, s)];
-  if (e.second < bytes) {
-    if (e.first) {
-      if (int rc = check_hip(h, hipStreamSynchronize(s), "token slab sync")) return rc;
-      (void)hipFree(e.first);
-      e = {nullptr, 0};
-    }
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) return set_error(h, RR_EWORKSPACE, "rr_token_pool: cannot allocate the partial slabs");
-    e = {(float*)p, bytes};
-  }
-  *out = e.first;
-  return RR_OK;
 }
 
 template <int NV>
@@ -433,24 +351,18 @@ extern "C" int rr_token_pool(rr_handle_t h, const float* x, int b, int hw, int c
     return set_error(h, RR_EINVAL,
                      "rr_token_pool: bad argument (c % 256 == 0, 256 <= c <= 1024, 1 <= n_obj <= 8, hw >= 1, 16-B aligned)");
   if (b == 0) return RR_OK;
-  // an image's positions are split over workgroups only while whole images
-  // leave the chip short of work; the split depends on (b, hw) alone
-  int splits = 1, chunk = hw;
-  if (b < kTokTargetBlocks) {
-    const int want = (kTokTargetBlocks + b - 1) / b;
-    const int most = (hw + kTokMinPixels - 1) / kTokMinPixels;
-    splits = want < most ? want : most;
-    chunk = (hw + splits - 1) / splits;
-    splits = (hw + chunk - 1) / chunk;
-  }
+  const auto [splits, chunk] = split_positions(b, hw, kTokMinPixels, kTokTargetBlocks);
   const long long blocks = (long long)b * splits;
   const long long len = (long long)n_obj * c;
   if (blocks > 0x7fffffffLL || (long long)b * (len >> 8) > 0x7fffffffLL)
     return set_error(h, RR_EINVAL, "rr_token_pool: too many images");
   hipStream_t s = (hipStream_t)stream;
   float* dst = out;
-  if (splits > 1)
-    if (int rc = tok_slab_get(h, s, (size_t)blocks * len * sizeof(float), &dst)) return rc;
+  if (splits > 1) {
+    void* p = nullptr;
+    if (int rc = stream_scratch(h, s, (size_t)blocks * len * sizeof(float), &p, "rr_token_pool")) return rc;
+    dst = (float*)p;
+  }
   TimedLaunch tl(h, kTimeElem, s);
   switch (c >> 8) {
     case 1: launch_token_pool<1>(x, hw, chunk, splits, query, n_obj, dst, (unsigned)blocks, s); break;
@@ -459,11 +371,8 @@ extern "C" int rr_token_pool(rr_handle_t h, const float* x, int b, int hw, int c
     default: launch_token_pool<4>(x, hw, chunk, splits, query, n_obj, dst, (unsigned)blocks, s); break;
   }
   if (int rc = check_hip(h, hipGetLastError(), "token_pool launch")) return rc;
-  if (splits > 1) {
-    hipLaunchKernelGGL(token_pool_sum_kernel, dim3((unsigned)(b * (len >> 8))), dim3(kTokSumWaves * 64), 0, s, dst, splits,
-                       (int)len, out);
-    return check_hip(h, hipGetLastError(), "token_pool_sum launch");
-  }
+  if (splits > 1)
+    return check_hip(h, launch_slab_sum<false>(dst, b, splits, (int)len, hw, out, s), "token_pool_sum launch");
   return RR_OK;
 }
 

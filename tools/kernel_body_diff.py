@@ -6,8 +6,10 @@ usage: python tools/kernel_body_diff.py OLD.s [OLD2.s ...] -- NEW.s [NEW2.s ...]
 
 A body runs from the kernel's label to its .Lfunc_end.  Normalised away: the
 kernel's own mangled name (template parameters may be renamed or dropped), the
-.LBB<n>_ function index, trailing ; comments and the mangled name of the
-per-file zero page s3_zero_src.  Prints the kernel counts and whether the
+.LBB<n>_ function index, trailing ; comments, the mangled name of the
+per-file zero page s3_zero_src and the directive that returns to the kernel's
+text section after its descriptor (.text for a plain kernel, a comdat .section
+for a template instance: a kernel may become one).  Prints the kernel counts and whether the
 multisets are equal; otherwise the demangled names on either side whose body
 has no partner (exit status 1).  CPU only."""
 import collections
@@ -33,6 +35,7 @@ def bodies(path):
             ln = txt[j].split(";")[0].rstrip().replace(n, "KERNEL")
             ln = re.sub(r"\.LBB\d+_", ".LBB_", ln)
             ln = re.sub(r"_ZN2rrL?11s3_zero_srcE[\w.$]*", "ZEROSRC", ln)
+            ln = re.sub(r"^\s*\.section\s+\.text\.KERNEL,.*$", "\t.text", ln)
             if ln.strip():
                 body.append(ln)
             j += 1
