@@ -70,7 +70,11 @@ typedef struct rr_handle_s* rr_handle_t;
  * as well: no existing entry changed, so a caller built against the earlier
  * revision-7 header still passes the right arguments everywhere; likewise
  * rr_attention_hd128, rr_token_pool and rr_gelu (the Token head), and
- * rr_how_vlad and rr_how_asmk (the HOW head's aggregations).
+ * rr_how_vlad and rr_how_asmk (the HOW head's aggregations), and the native
+ * trunk plan's rr_trunk_h2_* entries, rr_timing_collect_ex and the tuning key
+ * RR_TUNE_TRUNK_PARTS (16); rr_timing_collect keeps its arguments and now
+ * returns the UNION of the class's launch intervals (equal to the former sum
+ * on one stream; see below).
  * Bindings compare rr_abi_version() with the RR_ABI_VERSION they were
  * written against.                                                          */
 #define RR_ABI_VERSION 7
@@ -90,9 +94,21 @@ const char* rr_last_error(rr_handle_t h);
  *          1 = conv/linear GEMM, 2 = top-k select/merge,
  *          3 = elementwise (preprocess/resize/pool/norm),
  *          4 = dense cosine GEMM (top-k threshold seed, rr_cosine_scores),
- *          5 = fused attention (ViT). */
+ *          5 = fused attention (ViT).
+ * The milliseconds are the length of the UNION of the class's launch
+ * intervals: every launch's [start, stop] event pair is placed on one time
+ * axis, as offsets from the class's first start event, and overlapping
+ * intervals count once.  On one stream the intervals are disjoint and this is
+ * the sum of the per-launch durations, as before; when launches of a class
+ * co-run on several streams (the two-part trunk plan below) it is the time
+ * during which the class occupied the chip, so a class time never exceeds the
+ * wall time of the window.  The launch count is the number of launches.
+ * rr_timing_collect_ex returns, from the same events, the union and the plain
+ * sum of the per-launch durations (sum_ms >= union_ms; equal on one stream up
+ * to the float rounding of the offsets); either pointer may be NULL. */
 int rr_timing_enable(rr_handle_t h, int enable);
 int rr_timing_collect(rr_handle_t h, int cls, double* ms, long long* launches);
+int rr_timing_collect_ex(rr_handle_t h, int cls, double* union_ms, double* sum_ms, long long* launches);
 
 /* The device a handle was created for (rr_create's `device`). */
 int rr_get_device(rr_handle_t h, int* device);
@@ -150,6 +166,10 @@ int rr_get_device(rr_handle_t h, int* device);
  *                     for cout 64, 16 x 32 outputs of one image; no residual epilogue):
  *                     -1 = where no raster halo tile holds the map (the library's pick),
  *                     1 = wherever one serves, 0 = never (ABI 6, round 6)
+ *   RR_TUNE_TRUNK_PARTS: the native trunk plan (rr_trunk_h2_forward_u8): 1 = the whole
+ *                     batch on the caller's stream, 2 = two parts on the plan's two
+ *                     streams, -1 = the library's pick (the rule stated at
+ *                     rr_trunk_h2_parts)
  * Any other key or value: RR_EINVAL. */
 #define RR_TUNE_GEMM_CFG 1
 #define RR_TUNE_GEMM_BK 2
@@ -165,6 +185,7 @@ int rr_get_device(rr_handle_t h, int* device);
 #define RR_TUNE_S3_CFG_RES 13
 #define RR_TUNE_SWEEP_FORM 14
 #define RR_TUNE_HALO_2D 15
+#define RR_TUNE_TRUNK_PARTS 16
 int rr_set_tuning(rr_handle_t h, int key, int value);
 
 /* ---- search (ranker) ----------------------------------------------------
@@ -704,6 +725,97 @@ int rr_how_vlad(rr_handle_t h, const float* x, int b, int n, int d,
 int rr_how_asmk(rr_handle_t h, const float* x, int b, int n, int d,
                 const float* centroids, const float* weights, int k,
                 float* out, void* stream);
+
+/* ---- native ResNet trunk plan (f16x2 core) -------------------------------
+ * One call per forward for the whole bottleneck-ResNet trunk (torchvision
+ * children[:-2], networks/backbone.py:60-109, or ResNet_DOLG :218-274) from
+ * uint8 pixels: rr_preprocess_u8_ex (out_c 4), rr_amax_f32, the stem
+ * (rr_stem_pool_h2, or rr_conv2d_h2 + rr_maxpool2d), then per bottleneck
+ * conv1, conv2 and conv3 through rr_conv2d_h2 (a stage's first block: its
+ * downsample projection first, or conv3 + projection as one
+ * rr_bottleneck_out_h2), every conv reading its input's max-|x| record and
+ * publishing its output's.  The plan adds no kernel: it issues exactly these
+ * entry points, so the result is the same bits as calling them one by one.
+ *
+ * desc lists the convs in execution order: the stem, then per block
+ * [downsample, only in a stage's first block when fuse_entry[stage] == 0,]
+ * conv1, conv2, conv3.  With fuse_entry[stage] != 0 the first block's conv3
+ * entry holds rr_split2_f16 of the concatenated rows [W3 | Wd] (cin = planes +
+ * the block's input channels, bias = the two biases' sum, stride = the
+ * block's stride), as rr_bottleneck_out_h2 takes them.  All pointers are
+ * device pointers the caller keeps alive as long as the plan; the desc itself
+ * is copied.  rr_trunk_h2_create checks the channel chain and the strides
+ * against blocks[] and stride_on (RR_EINVAL otherwise).
+ *
+ * Parts.  A forward runs the batch in one part on the caller's stream, or cut
+ * in two at B / 2 (part 0 = images [0, B / 2)) on the plan's two non-blocking
+ * streams: both wait on an event recorded on the caller's stream, part 1
+ * also on an event part 0 records after its lag-th conv (the stem is conv 0,
+ * unfused downsample projections are not counted; a lag past the last conv
+ * means no such wait), and the caller's stream waits on both at the end.  The
+ * host issues the two parts' launches alternately.  The parts then run side by
+ * side about one layer apart, and the last, partly filled round of one
+ * part's kernel is filled with the other part's blocks.  Each part is exactly
+ * the one-part forward of its images, its split scales taken from its own
+ * max-|x| records, written straight into its rows of out_x4 / out_x3.
+ * rr_trunk_h2_parts returns what a forward will choose: RR_TUNE_TRUNK_PARTS when
+ * set to 1 or 2 (2 needs B >= 2), else the library's pick, which is 2 only when
+ * each part still gives the last stage's output, [B / 2 * oh * ow rows] x cout
+ * in 256 x 256 tiles, at least two tiles per compute unit:
+ *   ceil((B / 2) oh ow / 256) * (cout / 256) >= 2 * CUs.
+ * (The last stage has the smallest map, so the fewest row tiles; below two
+ * tiles per CU a part's launch no longer fills the chip for two rounds, and
+ * what the split costs -- every weight plane streamed twice, twice as many
+ * partly filled last rounds -- outweighs the rounds it can fill.  R101, 224 x
+ * 224, 256 CUs: two parts from B = 660.)  One part touches no plan stream.
+ *
+ * images: uint8 [B][H][W][3], H, W >= 1 (B < 0, H < 1 or W < 1: RR_EINVAL);
+ * B == 0 is RR_OK with no launch.  out_x4 [B][oh][ow][cout]: each stride-2 step
+ * (the stem, its pool, every stage but the first) maps n to (n - 1) / 2 + 1,
+ * so a four-stage trunk gives ceil(H / 32) x ceil(W / 32) and x3 ceil(H / 16) x
+ * ceil(W / 16).  out_x4_amax: x4's max-|x| record
+ * (RR_AMAX_SLOTS words; zeroed by the call; with two parts both parts' last
+ * conv publish into it, which gives the element-wise max of the records the
+ * parts would have written alone).  out_x3 / out_x3_amax (both or neither,
+ * NULL to skip; needs >= 4 stages): the third stage's output and its record;
+ * with two parts that record is folded from the parts' records by rr_amax_f32
+ * after the join: it holds the same maximum, not the same words.
+ * workspace: rr_trunk_h2_workspace_size(plan, B, H, W, parts) bytes (parts 1
+ * or 2; 0 for a bad argument), 256-B aligned, RR_EWORKSPACE when short.  The
+ * plan's streams and events are shared by its forwards: calls on one plan are
+ * serialised on the host (a mutex), and two-part forwards of one plan run one
+ * after the other on the device.
+ * rr_trunk_h2_counters: out[0] = forwards, out[1] = two-part forwards,
+ * out[2] = launches, waits and records issued on the plan's own streams.    */
+#define RR_TRUNK_MAX_STAGES 8
+typedef struct rr_trunk_conv_s {
+  const void* w2;        /* rr_split2_f16 planes [2][cout][K] */
+  const float* w_iscale; /* [cout] */
+  const float* bias;     /* [cout] or NULL */
+  int cin, cout, kh, kw, stride, pad;
+  int residual; /* 1: adds the block's identity (conv3 of a block) */
+  int relu;
+} rr_trunk_conv_t;
+typedef struct rr_trunk_desc_s {
+  int n_stages;
+  int blocks[RR_TRUNK_MAX_STAGES];     /* bottlenecks per stage */
+  int fuse_entry[RR_TRUNK_MAX_STAGES]; /* first block: conv3 + projection as one GEMM */
+  int stride_on;                       /* 0: the 3x3 conv2 carries a block's stride, 1: the 1x1 conv1 */
+  int fuse_stem_pool;                  /* the stem, its ReLU and the max-pool as one launch (stem cout 64) */
+  int lag;                             /* part 1 starts after part 0's lag-th conv (>= 0; 1 is the measured default) */
+  float mean[3], std[3];               /* rr_preprocess_u8's */
+  int n_convs;
+  const rr_trunk_conv_t* convs;
+} rr_trunk_desc_t;
+typedef struct rr_trunk_plan_s* rr_trunk_plan_t;
+int rr_trunk_h2_create(rr_handle_t h, const rr_trunk_desc_t* desc, rr_trunk_plan_t* out);
+int rr_trunk_h2_destroy(rr_handle_t h, rr_trunk_plan_t plan);
+size_t rr_trunk_h2_workspace_size(rr_trunk_plan_t plan, int b, int hgt, int wid, int parts);
+int rr_trunk_h2_parts(rr_handle_t h, rr_trunk_plan_t plan, int b, int hgt, int wid);
+int rr_trunk_h2_counters(rr_trunk_plan_t plan, long long* out3);
+int rr_trunk_h2_forward_u8(rr_handle_t h, rr_trunk_plan_t plan, const uint8_t* img_nhwc, int b, int hgt, int wid,
+                           float* out_x4, unsigned* out_x4_amax, float* out_x3, unsigned* out_x3_amax,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -24,8 +24,24 @@ TIME_COSINE, TIME_GEMM, TIME_SELECT, TIME_ELEM, TIME_COSINE_SEED, TIME_ATTN = 0,
 # rr_set_tuning keys
 # (6, 7 and 12 -- sweep_order, sweep_pf, lp_il -- were retired in ABI 5)
 TUNE_GEMM_CFG, TUNE_GEMM_BK, TUNE_LP_CFG, TUNE_S3_CFG, TUNE_S3_STAGGER, \
-    TUNE_SWEEP_MF16, TUNE_SWEEP_IL, TUNE_CONV_IL, TUNE_HALO_MF, TUNE_S3_CFG_RES, TUNE_SWEEP_FORM, TUNE_HALO_2D = \
-    1, 2, 3, 4, 5, 8, 9, 10, 11, 13, 14, 15
+    TUNE_SWEEP_MF16, TUNE_SWEEP_IL, TUNE_CONV_IL, TUNE_HALO_MF, TUNE_S3_CFG_RES, TUNE_SWEEP_FORM, TUNE_HALO_2D, \
+    TUNE_TRUNK_PARTS = 1, 2, 3, 4, 5, 8, 9, 10, 11, 13, 14, 15, 16
+TRUNK_MAX_STAGES = 8  # RR_TRUNK_MAX_STAGES
+
+
+class TrunkConv(ctypes.Structure):
+    """rr_trunk_conv_t"""
+    _fields_ = [("w2", ctypes.c_void_p), ("w_iscale", ctypes.c_void_p), ("bias", ctypes.c_void_p),
+                ("cin", ctypes.c_int), ("cout", ctypes.c_int), ("kh", ctypes.c_int), ("kw", ctypes.c_int),
+                ("stride", ctypes.c_int), ("pad", ctypes.c_int), ("residual", ctypes.c_int), ("relu", ctypes.c_int)]
+
+
+class TrunkDesc(ctypes.Structure):
+    """rr_trunk_desc_t"""
+    _fields_ = [("n_stages", ctypes.c_int), ("blocks", ctypes.c_int * TRUNK_MAX_STAGES),
+                ("fuse_entry", ctypes.c_int * TRUNK_MAX_STAGES), ("stride_on", ctypes.c_int),
+                ("fuse_stem_pool", ctypes.c_int), ("lag", ctypes.c_int), ("mean", ctypes.c_float * 3),
+                ("std", ctypes.c_float * 3), ("n_convs", ctypes.c_int), ("convs", ctypes.POINTER(TrunkConv))]
 
 _lib = None
 _lock = threading.RLock()
@@ -45,6 +61,14 @@ SIGNATURES = {
     "rr_last_error": (ctypes.c_char_p, [_vp]),
     "rr_timing_enable": (_i, [_vp, _i]),
     "rr_timing_collect": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_ll)]),
+    "rr_timing_collect_ex": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                  ctypes.POINTER(_ll)]),
+    "rr_trunk_h2_create": (_i, [_vp, _vp, ctypes.POINTER(_vp)]),
+    "rr_trunk_h2_destroy": (_i, [_vp, _vp]),
+    "rr_trunk_h2_workspace_size": (_sz, [_vp, _i, _i, _i, _i]),
+    "rr_trunk_h2_parts": (_i, [_vp, _vp, _i, _i, _i]),
+    "rr_trunk_h2_counters": (_i, [_vp, ctypes.POINTER(_ll)]),
+    "rr_trunk_h2_forward_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "rr_get_device": (_i, [_vp, ctypes.POINTER(_i)]),
     "rr_set_tuning": (_i, [_vp, _i, _i]),
     "rr_cosine_topk_workspace_size": (_sz, [_i, _ll, _i, _i]),

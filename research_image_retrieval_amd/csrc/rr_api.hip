@@ -111,11 +111,7 @@ const char* rr_last_error(rr_handle_t h) { return h ? h->last_error.c_str() : "n
 int rr_timing_enable(rr_handle_t h, int enable) {
   RR_ENTRY(h);
   h->timing = enable != 0;
-  for (int c = 0; c < rr_handle_s::kClasses; ++c) {
-    h->n_ev[c] = 0;
-    h->acc_ms[c] = 0;
-    h->acc_launches[c] = 0;
-  }
+  for (int c = 0; c < rr_handle_s::kClasses; ++c) h->n_ev[c] = 0;
   return RR_OK;
 }
 
@@ -181,29 +177,60 @@ int rr_set_tuning(rr_handle_t h, int key, int value) {
       if (!in({-1, 0, 1})) break;
       h->tune.halo_2d = value;
       return RR_OK;
+    case RR_TUNE_TRUNK_PARTS:
+      if (!in({-1, 1, 2})) break;
+      h->tune.trunk_parts = value;
+      return RR_OK;
     default:
       return set_error(h, RR_EINVAL, "rr_set_tuning: unknown key");
   }
   return set_error(h, RR_EINVAL, "rr_set_tuning: value out of range for this key");
 }
 
-int rr_timing_collect(rr_handle_t h, int cls, double* ms, long long* launches) {
+// The class's launch intervals on one time axis (offsets from its first start
+// event): the length of their union, and the plain sum of their durations.
+// Sorted by start, an interval that begins at or after everything before it
+// has ended adds its own duration, so on one stream, where launch order is
+// start order and the intervals are disjoint, the union is the same sum of the
+// same terms in the same order.
+int rr_timing_collect_ex(rr_handle_t h, int cls, double* union_ms, double* sum_ms, long long* launches) {
   if (!h || cls < 0 || cls >= rr_handle_s::kClasses) return RR_EINVAL;
   DeviceGuard dg(h);
-  for (int i = 0; i < h->n_ev[cls]; ++i) {
+  const int n = h->n_ev[cls];
+  struct Span {
+    double start, dur;
+  };
+  std::vector<Span> spans;
+  spans.reserve(n);
+  double sum = 0;
+  for (int i = 0; i < n; ++i) {
     if (int rc = check_hip(h, hipEventSynchronize(h->ev_stop[cls][i]), "timing sync")) return rc;
-    float t = 0.f;
+    float t = 0.f, off = 0.f;
     if (int rc = check_hip(h, hipEventElapsedTime(&t, h->ev_start[cls][i], h->ev_stop[cls][i]), "timing elapsed"))
       return rc;
-    h->acc_ms[cls] += t;
-    h->acc_launches[cls] += 1;
+    if (i > 0)
+      if (int rc = check_hip(h, hipEventElapsedTime(&off, h->ev_start[cls][0], h->ev_start[cls][i]), "timing offset"))
+        return rc;
+    spans.push_back({(double)off, (double)t});
+    sum += t;
+  }
+  std::stable_sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.start < b.start; });
+  double uni = 0, end = 0;
+  for (int i = 0; i < n; ++i) {
+    const double e = spans[i].start + spans[i].dur;
+    if (i == 0 || spans[i].start >= end) uni += spans[i].dur;
+    else if (e > end) uni += e - end;
+    if (i == 0 || e > end) end = e;
   }
   h->n_ev[cls] = 0;
-  if (ms) *ms = h->acc_ms[cls];
-  if (launches) *launches = h->acc_launches[cls];
-  h->acc_ms[cls] = 0;
-  h->acc_launches[cls] = 0;
+  if (union_ms) *union_ms = uni;
+  if (sum_ms) *sum_ms = sum;
+  if (launches) *launches = n;
   return RR_OK;
+}
+
+int rr_timing_collect(rr_handle_t h, int cls, double* ms, long long* launches) {
+  return rr_timing_collect_ex(h, cls, ms, nullptr, launches);
 }
 
 size_t rr_cosine_topk_workspace_size(int nq, long long n, int d, int k) {

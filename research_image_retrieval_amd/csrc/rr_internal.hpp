@@ -31,6 +31,7 @@ struct rr_handle_s {
     int halo_2d = -1;      // the 2-D block halo tiles: -1 where no raster halo holds the map, 1 wherever one serves, 0 never
     int s3_cfg_res = 0;    // split cores: forced tile config for the GEMMs with a residual epilogue only (0: s3_cfg's)
     int sweep_form = -1;   // bf16 filter sweeps: 0 = gemm_lp.hip's tiles, 1 / 2 = sweep16.hip on 128-B / 64-B LDS rows; -1: the pick
+    int trunk_parts = -1;  // native trunk plan (trunk_plan.hip): 1 = one part, 2 = two parts on two streams; -1: the pick (rr.h's rule)
   } tune;
   int n_cu = 0;  // compute units of the handle's device (device_cu_count)
   // timing (see rr_timing_enable)
@@ -41,8 +42,6 @@ struct rr_handle_s {
   // pool silently dropped the launches past it)
   std::vector<hipEvent_t> ev_start[kClasses], ev_stop[kClasses];
   int n_ev[kClasses] = {};
-  double acc_ms[kClasses] = {};
-  long long acc_launches[kClasses] = {};
   // the extractor heads' per-stream scratch (heads_common.hpp: stream_scratch);
   // rr_destroy frees it
   std::map<hipStream_t, std::pair<void*, size_t>> scratch;

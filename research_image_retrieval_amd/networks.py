@@ -74,6 +74,17 @@ class ResNet:
         w, b = self.convs[name]
         return ops.conv2d(x, w, b, stride, pad, residual, relu)
 
+    def plan(self, lag=1):
+        """The f16x2 trunk as a native plan (ops.TrunkPlan, built on first use,
+        one per lag): uint8 pixels -> x4 (x3) and their records in one call, the
+        same launches as _forward_h2 under the current fuse_downsample /
+        fuse_stem_pool."""
+        plans = self.__dict__.setdefault("_plans", {})
+        key = (lag, bool(self.fuse_downsample), bool(self.fuse_stem_pool))
+        if key not in plans:
+            plans[key] = ops.TrunkPlan(self, lag)
+        return plans[key]
+
     def _forward_h2(self, x, return_x3, hook=None, return_x3_amax=False, return_amax=False):
         """The trunk on the f16x2 core: every conv reads its input's max-|x|
         record and writes its output's (one zeroed [2 + 3 blocks, 64] tensor per
@@ -200,11 +211,34 @@ class _Extractor:
     def forward_test(self, x):
         return self.forward_test_nhwc(self._input(x))
 
+    # A ResNet-based extractor names its trunk and what follows it, so that
+    # forward_test_u8 can run the trunk as the native plan (ResNet.plan):
+    # _trunk() -> the networks.ResNet (None: no such trunk), _needs_x3: the tail
+    # reads layer3's output, _tail(x3, x4, x3_amax, x4_amax) -> descriptors.
+    _needs_x3 = False
+
+    def _trunk(self):
+        return None
+
+    def _tail(self, x3, x4, x3_amax, x4_amax):
+        raise NotImplementedError
+
     @torch.no_grad()
     def forward_test_u8(self, img_nhwc_u8):
         """uint8 [B,H,W,3] pixels -> descriptors, with ToTensor+Normalize fused
-        into the first kernel (dataset/configdataset.py:417)."""
-        return self.forward_test_nhwc(ops.preprocess_u8(img_nhwc_u8, out_c=self.in_channels))
+        into the first kernel (dataset/configdataset.py:417).  A ResNet-based
+        extractor on the f16x2 core runs its trunk as one native call
+        (ops.TrunkPlan: the launches of ResNet._forward_h2, in two parts on two
+        streams where the batch is large enough) and its tail on the current
+        stream after the plan's join."""
+        x = img_nhwc_u8
+        t = self._trunk()
+        if t is not None and t.conv_math == "h2":
+            if self._needs_x3:
+                return self._tail(*t.plan().forward_u8(x, return_x3=True))
+            x4, x4a = t.plan().forward_u8(x)
+            return self._tail(None, x4, None, x4a)
+        return self.forward_test_nhwc(ops.preprocess_u8(x, out_c=self.in_channels))
 
     @torch.no_grad()
     def forward_test_u8_streams(self, img_nhwc_u8, streams, lag=1):
@@ -281,11 +315,16 @@ class GeM(_Extractor):
         self.whiten_b = wb.float().contiguous().to(self.device)
         self.outputdim = outputdim
 
-    def forward_test_nhwc(self, x_nhwc, hook=None):
-        f = self.backbone(x_nhwc, hook=hook)
-        f = self.pooling(f)
+    def _trunk(self):
+        return self.backbone
+
+    def _tail(self, x3, x4, x3_amax, x4_amax):
+        f = self.pooling(x4)
         f = ops.linear(f, self.whiten_w, self.whiten_b)
         return ops.l2_normalize(f, EPS_L2, out=f)
+
+    def forward_test_nhwc(self, x_nhwc, hook=None):
+        return self._tail(None, self.backbone(x_nhwc, hook=hook), None, None)
 
 
 class DOLG(_Extractor):
@@ -352,6 +391,14 @@ class DOLG(_Extractor):
         else:
             (x3, x4), x3a = self.globalmodel(x_nhwc, return_x3=True), None
         return self.head(x3, x4, x3a)
+
+    _needs_x3 = True
+
+    def _trunk(self):
+        return self.globalmodel
+
+    def _tail(self, x3, x4, x3_amax, x4_amax):
+        return self.head(x3, x4, x3_amax)
 
     def head(self, x3, x4, x3_amax=None):
         """Everything after the trunk: (x3, x4) NHWC -> descriptors [B,512]."""
@@ -447,6 +494,12 @@ class SOLAR(_Extractor):
         else:
             x4, x4a = self.backbone(x_nhwc), None
         return self.tail(self.pooling(x4, x4a))
+
+    def _trunk(self):
+        return self.backbone
+
+    def _tail(self, x3, x4, x3_amax, x4_amax):
+        return self.tail(self.pooling(x4, x4_amax))
 
     def tail(self, pooled):
         """:587-590: F.normalize -> whiten -> F.normalize on the pooled [B,2048]."""
@@ -594,6 +647,12 @@ class Token(_Extractor):
             x4, x4a = self.backbone(x_nhwc), None
         return self.tail(self.tr(x4, x4a))
 
+    def _trunk(self):
+        return self.backbone
+
+    def _tail(self, x3, x4, x3_amax, x4_amax):
+        return self.tail(self.tr(x4, x4_amax))
+
     def tail(self, f):
         """:304: F.normalize on the head's [B,1024]."""
         return ops.l2_normalize(f, EPS_L2, out=f)
@@ -677,11 +736,20 @@ class GeMPCAw(_Extractor):
         self.net = net
         self.pcaw = pcaw
         self.outputdim = pcaw.dim
+        self._needs_x3 = net._needs_x3
 
-    def forward_test_nhwc(self, x_nhwc, hook=None):
-        f = self.net.forward_test_nhwc(x_nhwc, hook=hook)
+    def _trunk(self):
+        return self.net._trunk()
+
+    def _whiten(self, f):
         f = self.pcaw(f)
         return ops.l2_normalize(f, EPS_L2, out=f)
+
+    def _tail(self, x3, x4, x3_amax, x4_amax):
+        return self._whiten(self.net._tail(x3, x4, x3_amax, x4_amax))
+
+    def forward_test_nhwc(self, x_nhwc, hook=None):
+        return self._whiten(self.net.forward_test_nhwc(x_nhwc, hook=hook))
 
 
 class VisionTransformer(_Extractor):

@@ -239,6 +239,129 @@ def bottleneck_out_h2(y, y_amax, x, x_amax, wb, stride, out_amax=None):
     return out
 
 
+class TrunkPlan:
+    """A networks.ResNet's f16x2 trunk as one native call per forward
+    (rr_trunk_h2_*, include/rr.h): uint8 pixels -> x4 (and x3) with their
+    max-|x| records, through the launches ResNet._forward_h2 issues, for the
+    whole batch on the current stream or, where the batch is large enough
+    (rr.h's rule; ``ops.tuning(dev, trunk_parts=1 | 2)`` forces it), in two
+    parts on the plan's two streams, part 1 ``lag`` convs behind part 0.  The
+    plan reads the ResNet's split weights in place, so it keeps the net
+    alive."""
+
+    def __init__(self, net, lag=1):
+        if net.conv_math != "h2":
+            raise ValueError("TrunkPlan: the native plan runs the f16x2 trunk (conv_math='h2')")
+        from . import weights as W
+        self.net = net
+        self.dev = _dev(net.convs["conv1"][0])
+        cv, h2 = net.convs, net.convs_h2
+        fuse_stem = bool(net.fuse_stem_pool and h2["conv1"].cout == 64)
+        convs = []
+
+        def add(wc, bias, stride, pad, residual, relu, cin=None):
+            convs.append(_lib.TrunkConv(wc.planes.data_ptr() if isinstance(wc, H2Conv) else wc.planes2.data_ptr(),
+                                        wc.iscale.data_ptr(), None if bias is None else bias.data_ptr(),
+                                        wc.cin if cin is None else cin, wc.cout, getattr(wc, "kh", 1),
+                                        getattr(wc, "kw", 1), stride, pad, int(residual), int(relu)))
+
+        add(h2["conv1"], cv["conv1"][1], 2, 3, False, True)
+        fuse_entry = []
+        for li, nb in enumerate(net.layers):
+            for bi in range(nb):
+                p = f"layer{li + 1}.{bi}"
+                stride = 2 if (bi == 0 and li > 0) else 1
+                s1, s2 = W.block_strides(stride, net.stride_on)
+                fused = bi == 0 and net.fuse_downsample and p in net.bneck_h2
+                if bi == 0:
+                    fuse_entry.append(int(fused))
+                    if not fused:
+                        d = f"{p}.downsample.0"
+                        add(h2[d], cv[d][1], stride, 0, False, False)
+                add(h2[f"{p}.conv1"], cv[f"{p}.conv1"][1], s1, 0, False, True)
+                add(h2[f"{p}.conv2"], cv[f"{p}.conv2"][1], s2, 1, False, True)
+                if fused:
+                    wb = net.bneck_h2[p]
+                    add(wb, wb.bias, stride, 0, False, True, cin=wb.planes + wb.cin)
+                else:
+                    add(h2[f"{p}.conv3"], cv[f"{p}.conv3"][1], 1, 0, True, True)
+        self._convs = (_lib.TrunkConv * len(convs))(*convs)
+        d = _lib.TrunkDesc()
+        d.n_stages = len(net.layers)
+        for i, nb in enumerate(net.layers):
+            d.blocks[i], d.fuse_entry[i] = nb, fuse_entry[i]
+        d.stride_on = 0 if net.stride_on == "3x3" else 1
+        d.fuse_stem_pool = int(fuse_stem)
+        d.lag = int(lag)
+        d.mean[:] = (0.485, 0.456, 0.406)
+        d.std[:] = (0.229, 0.224, 0.225)
+        d.n_convs = len(convs)
+        d.convs = ctypes.cast(self._convs, ctypes.POINTER(_lib.TrunkConv))
+        self.h = _lib.handle(self.dev)
+        self.out_c = convs[-1].cout
+        self.plan = ctypes.c_void_p()
+        _lib.check(_lib.lib().rr_trunk_h2_create(self.h, ctypes.byref(d), ctypes.byref(self.plan)), self.h,
+                   "rr_trunk_h2_create")
+
+    def __del__(self):
+        plan = getattr(self, "plan", None)
+        if plan:
+            self.plan = None
+            try:
+                _lib.lib().rr_trunk_h2_destroy(self.h, plan)
+            except Exception:  # interpreter shutdown: the module's globals may be gone
+                pass
+
+    def parts(self, b, h, w):
+        """The number of parts a forward of [b, h, w, 3] images will run in."""
+        n = _lib.lib().rr_trunk_h2_parts(self.h, self.plan, int(b), int(h), int(w))
+        if n < 0:
+            _lib.check(n, self.h, "rr_trunk_h2_parts")
+        return n
+
+    def counters(self):
+        """(forwards, two-part forwards, operations issued on the plan's own streams)."""
+        out = (ctypes.c_longlong * 3)()
+        _lib.check(_lib.lib().rr_trunk_h2_counters(self.plan, out), self.h, "rr_trunk_h2_counters")
+        return tuple(out)
+
+    def forward_u8(self, img_nhwc_u8, return_x3=False):
+        """uint8 [B,H,W,3] -> (x4, x4's record), or with
+        return_x3 (x3, x4, x3's record, x4's record), on the current stream."""
+        img = img_nhwc_u8
+        if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3:
+            raise ValueError("TrunkPlan.forward_u8: expected uint8 [B,H,W,3]")
+        if _dev(img) != self.dev:
+            raise ValueError("TrunkPlan.forward_u8: images on another device than the plan's weights")
+        img = img.contiguous()
+        b, h, w, _ = img.shape
+        if h < 1 or w < 1:
+            raise ValueError("TrunkPlan.forward_u8: empty images")
+        L = _lib.lib()
+
+        def halved(n, times):  # every stride-2 step (7x7/2 pad 3, 3x3/2 pad 1, 1x1/2) maps n to (n - 1) // 2 + 1
+            for _ in range(times):
+                n = (n - 1) // 2 + 1
+            return n
+
+        n2 = 1 + len(self.net.layers)  # the stem, its pool, every stage but the first
+        x4 = torch.empty((b, halved(h, n2), halved(w, n2), self.out_c), dtype=torch.float32, device=img.device)
+        # (the forward zeroes the records it publishes)
+        rec = torch.empty((2 if return_x3 else 1, AMAX_SLOTS), dtype=torch.int32, device=img.device) if b else \
+            amax_records(2 if return_x3 else 1, img.device)
+        x3 = None
+        if return_x3:
+            c3 = self.net.convs_h2[f"layer3.{self.net.layers[2] - 1}.conv3"].cout
+            x3 = torch.empty((b, halved(h, 4), halved(w, 4), c3), dtype=torch.float32, device=img.device)
+        if b:
+            nbytes = L.rr_trunk_h2_workspace_size(self.plan, b, h, w, self.parts(b, h, w))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
+            _lib.check(L.rr_trunk_h2_forward_u8(self.h, self.plan, _ptr(img), b, h, w, _ptr(x4), _ptr(rec[-1]),
+                                                _ptr(x3), _ptr(rec[0]) if return_x3 else None, _ptr(ws), nbytes,
+                                                _stream(self.dev)), self.h, "rr_trunk_h2_forward_u8")
+        return (x3, x4, rec[0], rec[1]) if return_x3 else (x4, rec[0])
+
+
 def resize_bilinear(x_nhwc, out_h, out_w, scale_factor=None):
     """NHWC bilinear resize, align_corners=False.  With ``scale_factor`` the
     source index uses 1/scale_factor, as F.interpolate(scale_factor=s) does."""
@@ -602,9 +725,10 @@ _TUNE_KEYS = {"gemm_cfg": _lib.TUNE_GEMM_CFG, "gemm_bk": _lib.TUNE_GEMM_BK, "lp_
               "s3_cfg": _lib.TUNE_S3_CFG, "s3_stagger": _lib.TUNE_S3_STAGGER, "sweep_mf16": _lib.TUNE_SWEEP_MF16,
               "sweep_il": _lib.TUNE_SWEEP_IL, "conv_il": _lib.TUNE_CONV_IL,
               "halo_mf": _lib.TUNE_HALO_MF, "s3_cfg_res": _lib.TUNE_S3_CFG_RES,
-              "sweep_form": _lib.TUNE_SWEEP_FORM, "halo_2d": _lib.TUNE_HALO_2D}
-_TUNE_DEFAULT = {"s3_stagger": -1, "sweep_mf16": -1, "sweep_il": -1,
-                 "conv_il": -1, "halo_mf": -1, "sweep_form": -1, "halo_2d": -1}  # the library's own pick (0 elsewhere)
+              "sweep_form": _lib.TUNE_SWEEP_FORM, "halo_2d": _lib.TUNE_HALO_2D,
+              "trunk_parts": _lib.TUNE_TRUNK_PARTS}
+_TUNE_DEFAULT = {"s3_stagger": -1, "sweep_mf16": -1, "sweep_il": -1, "conv_il": -1, "halo_mf": -1,
+                 "sweep_form": -1, "halo_2d": -1, "trunk_parts": -1}  # the library's own pick (0 elsewhere)
 
 
 class tuning:
@@ -646,6 +770,15 @@ class KernelTimer:
         _lib.check(_lib.lib().rr_timing_collect(self.h, cls, ctypes.byref(ms), ctypes.byref(n)), self.h,
                    "rr_timing_collect")
         return ms.value, n.value
+
+    def collect_ex(self, cls):
+        """(union ms, sum of the per-launch ms, launches): rr_timing_collect_ex.
+        collect() returns the union; the two differ where launches co-ran."""
+        uni, tot = ctypes.c_double(), ctypes.c_double()
+        n = ctypes.c_longlong()
+        _lib.check(_lib.lib().rr_timing_collect_ex(self.h, cls, ctypes.byref(uni), ctypes.byref(tot), ctypes.byref(n)),
+                   self.h, "rr_timing_collect_ex")
+        return uni.value, tot.value, n.value
 
 
 def linear_ex(x, w, bias=None, residual=None, act=0):
