@@ -70,7 +70,8 @@ typedef struct rr_handle_s* rr_handle_t;
  * as well: no existing entry changed, so a caller built against the earlier
  * revision-7 header still passes the right arguments everywhere; likewise
  * rr_attention_hd128, rr_token_pool and rr_gelu (the Token head), and
- * rr_how_vlad and rr_how_asmk (the HOW head's aggregations), and the native
+ * rr_how_vlad and rr_how_asmk (the HOW head's aggregations), rr_sos_cov and
+ * rr_linear_splitk (the SoSNet head: added, no existing entry changed), and the native
  * trunk plan's rr_trunk_h2_* entries, rr_timing_collect_ex and the tuning key
  * RR_TUNE_TRUNK_PARTS (16); rr_timing_collect keeps its arguments and now
  * returns the UNION of the class's launch intervals (equal to the former sum
@@ -725,6 +726,57 @@ int rr_how_vlad(rr_handle_t h, const float* x, int b, int n, int d,
 int rr_how_asmk(rr_handle_t h, const float* x, int b, int n, int d,
                 const float* centroids, const float* weights, int k,
                 float* out, void* stream);
+
+/* ---- SoSNet head (models/sosnet.py) -------------------------------------- */
+/* Attention-weighted, centred covariance pooling as its packed upper
+ * triangle.  z [b][n][c] fp32: the RAW rows of the second-order projection
+ * conv WITHOUT its bias (Wp x_p; the bias cancels under the centring); hid
+ * [b][n][dh]: the ReLU'd output of the attention MLP's second layer, w3 [dh]
+ * and b3 its last layer; per image
+ *   a_p  = sigmoid(w3 . hid_p + b3)          (hid == NULL: a = 1, use_attention=False)
+ *   y_p  = a_p z_p                           (= the projection of the attended row, minus bp)
+ *   cov  = sum_p (y_p - mean_p y)(y_p - mean_p y)^T / (n - 1)
+ *   out  = cov[i][j] for i <= j, row-major as torch.triu_indices(c, c):
+ *          off(i, j) = i c - i (i - 1) / 2 + (j - i)
+ *   inv_norm = 1 / max(||out row||_2, 1e-12)
+ * out [b][c (c + 1) / 2] is NOT normalised: the L2 over it commutes with the
+ * Linear that follows, whose reduce step takes inv_norm as its row scale
+ * (rr_linear_splitk).  att_out [b][n] (may be NULL) receives the a_p.
+ * Replaces SimilarityAttention.forward's last Linear, Sigmoid and multiply
+ * (:84-90) and SecondOrderPooling.forward's mean, centring, bmm, gather and
+ * F.normalize (:41-53).  The rows are centred BEFORE the product (a first
+ * launch leaves a_p and the mean in the heads' scratch, rr_dolg_local_pool),
+ * never as E[y y^T] - mu mu^T.  z is then read once per pair of 64-channel
+ * tiles (upper-triangle pairs only); the weighted rows, the centred rows and
+ * the square covariance never reach global memory; the Gram product runs on
+ * the exact-fp32 MFMA.  No float atomics: where b < 64 an image's positions are
+ * split over workgroups (a function of b and n only: at least 64 positions
+ * each) and the partial tiles, kept in the scratch, are added in index order;
+ * the sum of squares behind inv_norm is added in a fixed order as well: the
+ * same bits on every run.
+ * c % 32 == 0, 32 <= c <= 512; with hid: dh % 4 == 0, 4 <= dh <= 512;
+ * 2 <= n <= 65535 (n == 1: the reference divides by N - 1 = 0 and returns
+ * NaN); every pointer 16-B aligned (else RR_EINVAL, nothing written); b == 0
+ * is RR_OK and launches nothing; offsets are 64-bit.  Timing class 3.       */
+int rr_sos_cov(rr_handle_t h, const float* z, int b, int n, int c,
+               const float* hid, int dh, const float* w3, float b3,
+               float* att_out, float* out, float* inv_norm, void* stream);
+
+/* Split-K form of the skinny linear:
+ *   y[i][:] = act(row_scale[i] * (x_i . w^T) + bias),
+ * x [m][k], w [n][k], y [m][n]; row_scale [m] and bias [n] may be NULL; act as
+ * rr_linear_ex (0 none, 1 ReLU, 2 QuickGELU).  The k axis is cut into slices
+ * that the fp32 MFMA core computes side by side (its split-K mode, partials
+ * [m][slices][n] in the heads' scratch); a reduce kernel adds the slices in
+ * index order and applies the scale, the bias and the activation.  The slice
+ * count is a function of (m, k, n) and the device's compute-unit count only:
+ * the same bits on every run.  For few rows and a long k, where rr_linear
+ * leaves most of the chip idle (one workgroup per output tile walks all of k).
+ * k % 4 == 0, x / w 16-B aligned (else RR_EINVAL); m == 0 is RR_OK.  Timing
+ * class 1.                                                                   */
+int rr_linear_splitk(rr_handle_t h, const float* x, int m, int k,
+                     const float* w, int n, const float* row_scale,
+                     const float* bias, int act, float* y, void* stream);
 
 /* ---- native ResNet trunk plan (f16x2 core) -------------------------------
  * One call per forward for the whole bottleneck-ResNet trunk (torchvision

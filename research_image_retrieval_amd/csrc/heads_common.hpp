@@ -1,5 +1,5 @@
 // heads_common.hpp — what the extractor heads' files (dolg_ops.hip,
-// soa_ops.hip, token_ops.hip, how_ops.hip) share: the split of an image's
+// soa_ops.hip, token_ops.hip, how_ops.hip, sos_ops.hip) share: the split of an image's
 // positions over workgroups, the per-stream scratch their partial sums pass
 // through, the fixed-order adding kernel, the online-softmax tile step and the
 // launch with more than 64 KiB of dynamic LDS.
@@ -38,7 +38,9 @@ inline SplitPlan split_positions(int b, int n, int min_positions, int target_blo
 
 // The heads' scratch (the partial slabs of split images, ASMK's per-position
 // minima): one buffer per stream, owned by the handle and freed by rr_destroy.
-// rr_dolg_local_pool, rr_token_pool, rr_how_vlad and rr_how_asmk share the
+// rr_dolg_local_pool, rr_token_pool, rr_how_vlad, rr_how_asmk, rr_sos_cov (its
+// a_p, means, tile sums of squares and partial tiles) and rr_linear_splitk (its
+// k-slices' partial products) share the
 // buffer of their stream: launches on one stream are ordered, so the adding
 // (or counting) kernel of one call has read the buffer before the next call's
 // pooling kernel writes it; two streams never share one.  It grows on demand:

@@ -7,6 +7,10 @@ feature_dim=..., gem_p=...)`` returns a wrapper whose
 The HOW family (models/how_vlad.py:14-287) is served the same way:
 ``get_model('how_vlad_r50' | 'how_vlad_r101' | 'how_asmk_r50' | 'how_asmk_r101',
 num_classes, local_dim=..., num_clusters=...)``, [B, 2048] descriptors.
+SoSNet (models/sosnet.py:95-212) is built with ``get_sosnet_model(num_classes,
+backbone=..., second_order_dim=...)`` or ``SoSNetWrapper``; its registry names
+are NOT registered yet: ``get_model('sosnet_r50' | 'sosnet_r101', ...)`` still
+raises NotImplementedError (the names stay in OUT_OF_SCOPE).
 Training (``forward(x, targets)`` losses, optimizers) is out of scope
 (SURVEY.md §2 row 13): ``forward`` only produces eval-mode logits.
 """
@@ -279,6 +283,167 @@ def get_how_vlad_model(num_classes, backbone="resnet50", **kwargs):
 
 def get_how_asmk_model(num_classes, backbone="resnet50", **kwargs):
     return HOWASMKWrapper(num_classes=num_classes, backbone=backbone, **kwargs)
+
+
+class SoSNetModel(_Extractor):
+    """models/sosnet.py:95-183, eval mode: resnet trunk -> SimilarityAttention
+    (a per-position MLP 2048 -> 512 -> 256 -> 1, sigmoid, multiply) ->
+    SecondOrderPooling (1x1 conv 2048 -> second_order_dim, centred covariance
+    / (N - 1), packed upper triangle, F.normalize) -> feature_proj (Linear,
+    ReLU, Dropout as a no-op, Linear); extract_descriptor adds F.normalize.
+
+    Launches after the trunk: the attention MLP's first layer as a 1x1 conv
+    with ReLU and the projection conv, RAW and without its bias (conv_math
+    "h2": the f16x2 core on the trunk's max-|x| record; "f32": rr_conv2d);
+    rr_linear_ex 512 -> 256 with ReLU; rr_sos_cov (the last attention layer,
+    the sigmoid, the weighting, the centring, the covariance and the packing
+    in one kernel chain; y_p = a_p (Wp x_p) + bp, and bp cancels under the
+    centring); rr_linear_splitk with row_scale = rr_sos_cov's 1 / ||v|| and
+    ReLU (the L2 over the packed vector commutes with the Linear);
+    rr_linear; rr_l2_normalize.
+
+    Constructor: the reference's (backbone, pretrained, num_classes,
+    feature_dim, second_order_dim, use_attention), then state_dict (trunk keys
+    as networks.ResNet accepts, the reference's index-named nn.Sequential keys
+    included; head keys as weights.sos_head_from_state_dict), seed (synthetic
+    weights when state_dict is None), device, conv_math and stride_on as
+    GeMModel.  second_order_dim must fit rr_sos_cov (a multiple of 32 in
+    32..512): at 2048 the reference drops the projection and its first Linear
+    would hold 17 GB.
+
+    get_model("sosnet_r50" | "sosnet_r101") still raises NotImplementedError:
+    the names stay in OUT_OF_SCOPE and out of MODEL_REGISTRY (build the model
+    with get_sosnet_model)."""
+
+    in_channels = 4
+
+    def __init__(self, backbone="resnet50", pretrained=False, num_classes=1000, feature_dim=2048, second_order_dim=512,
+                 use_attention=True, state_dict=None, seed=0, device="cuda", conv_math="h2", stride_on="3x3"):
+        if pretrained:
+            raise ValueError("pretrained weights need a download; pass a local state_dict instead "
+                             "(models/sosnet.py:98 defaults to pretrained=True)")
+        if backbone not in ("resnet50", "resnet101"):
+            raise ValueError(f"Unsupported backbone: {backbone}")
+        c = second_order_dim
+        if c % 32 or not 32 <= c <= 512:
+            raise ValueError("SoSNetModel: second_order_dim % 32 == 0, 32 <= second_order_dim <= 512 (rr_sos_cov; at "
+                             "2048 the reference drops the projection and its first Linear would hold 17 GB)")
+        if state_dict is None:
+            head = W.sos_head_from_state_dict(W.synthetic_sos_head(seed + 1, c, num_classes, use_attention,
+                                                                   feature_dim))
+        else:
+            head = W.sos_head_from_state_dict(state_dict)
+        if ("att_w1" in head) != bool(use_attention):
+            raise ValueError("SoSNetModel: use_attention does not fit the state dict's head")
+        if head["proj_w"].shape[0] != c or head["fp0_w"].shape[0] != feature_dim:
+            raise ValueError("SoSNetModel: head weight shapes do not fit second_order_dim and feature_dim")
+        if use_attention and (head["att_w1"].shape[0] % 32 or head["att_w2"].shape[0] % 4 or
+                              not 4 <= head["att_w2"].shape[0] <= 512):
+            raise ValueError("SoSNetModel: the attention MLP's widths do not fit rr_sos_cov")
+        self.device = torch.device(device)
+        self.conv_math = conv_math
+        self.use_attention = bool(use_attention)
+        self.att_b3 = float(head.pop("att_b3")[0]) if use_attention else 0.0  # read on the host, before any device work
+        self.backbone = ResNet(backbone, state_dict, seed, device, conv_math=conv_math, stride_on=stride_on)
+        if head["proj_w"].shape[1] != self.backbone.outputdim_block5:
+            raise ValueError("SoSNetModel: second_order_pool.proj does not fit the trunk")
+        self.w = {k: v.to(self.device) for k, v in head.items()}
+        self.proj_w = self.w["proj_w"].view(c, 1, 1, -1)
+        self.proj_h2 = ops.H2Conv(self.proj_w) if conv_math == "h2" else None
+        if use_attention:
+            self.att_w1 = self.w["att_w1"].view(self.w["att_w1"].shape[0], 1, 1, -1)
+            self.att_h2 = ops.H2Conv(self.att_w1) if conv_math == "h2" else None
+        self.second_order_dim, self.feature_dim = c, feature_dim
+        self.outputdim = feature_dim
+
+    def _conv(self, x4, x4_amax, w, wc, bias, relu):
+        if self.conv_math == "h2":
+            return ops.conv2d_h2(x4, x4_amax, wc, bias, 1, 0, None, relu)
+        return ops.conv2d(x4, w, bias, 1, 0, None, relu)
+
+    def head(self, x4, x4_amax=None, taps=None):
+        """x4 NHWC -> features [B,feature_dim] (:144-161).  taps: a dict that
+        receives att [B,N] (use_attention), cov (the packed triangle,
+        un-normalised), inv_norm [B], hidden (after feature_proj's ReLU) and
+        features (tests)."""
+        b, n = x4.shape[0], x4.shape[1] * x4.shape[2]
+        if n < 2:
+            raise ValueError("SoSNetModel: a map with one position has no covariance (the reference divides by "
+                             "N - 1 = 0 and returns NaN, models/sosnet.py:45)")
+        if self.conv_math == "h2" and x4_amax is None:
+            x4_amax = ops.amax_f32(x4, ops.amax_records(1, x4.device)[0])
+        hid = None
+        if self.use_attention:
+            h1 = self._conv(x4, x4_amax, self.att_w1, self.att_h2, self.w["att_b1"], True)
+            hid = ops.linear_ex(h1.view(b * n, -1), self.w["att_w2"], self.w["att_b2"], act=1).view(b, n, -1)
+        z = self._conv(x4, x4_amax, self.proj_w, self.proj_h2, None, False).view(b, n, -1)
+        got = ops.sos_cov(z, hid, self.w.get("att_w3"), self.att_b3, want_att=taps is not None)
+        hidden = ops.linear_splitk(got[0], self.w["fp0_w"], self.w["fp0_b"], row_scale=got[1], act=1)
+        f = ops.linear(hidden, self.w["fp3_w"], self.w["fp3_b"])
+        if taps is not None:
+            taps.update(att=got[2], cov=got[0], inv_norm=got[1], hidden=hidden, features=f)
+        return f
+
+    def _trunk(self, x_nhwc, hook=None):
+        if self.conv_math == "h2":
+            return self.backbone(x_nhwc, hook=hook, return_amax=True)
+        return self.backbone(x_nhwc), None
+
+    def extract_features_nhwc(self, x_nhwc, hook=None):
+        return self.head(*self._trunk(x_nhwc, hook))
+
+    @torch.no_grad()
+    def extract_features(self, x):
+        return self.extract_features_nhwc(self._input(x))
+
+    def forward_test_nhwc(self, x_nhwc, hook=None):
+        f = self.extract_features_nhwc(x_nhwc, hook)
+        return ops.l2_normalize(f, EPS_L2, out=f)
+
+    @torch.no_grad()
+    def extract_descriptor(self, x):
+        return self.forward_test(x)
+
+    @torch.no_grad()
+    def forward(self, x, targets=None):
+        feats = self.extract_features(x)
+        return None, ops.linear(feats, self.w["cls_w"], self.w["cls_b"])
+
+    __call__ = forward
+
+
+class SoSNetWrapper(_Extractor):
+    """models/sosnet.py:186-212: training-loop facade over SoSNetModel."""
+
+    in_channels = 4
+
+    def __init__(self, num_classes, backbone="resnet50", feature_dim=2048, second_order_dim=512, use_attention=True,
+                 **kw):
+        self.backbone = SoSNetModel(backbone=backbone, num_classes=num_classes, feature_dim=feature_dim,
+                                    second_order_dim=second_order_dim, use_attention=use_attention, **kw)
+        self.outputdim = self.backbone.outputdim
+
+    def forward_test_nhwc(self, x_nhwc, hook=None):
+        return self.backbone.forward_test_nhwc(x_nhwc, hook)
+
+    @torch.no_grad()
+    def forward(self, x, targets=None):
+        return self.backbone(x)
+
+    __call__ = forward
+
+    def extract_features(self, x):
+        return self.backbone.extract_features(x)
+
+    def extract_descriptor(self, x):
+        return self.backbone.extract_descriptor(x)
+
+    def extract_global_descriptor(self, x):
+        return self.backbone.extract_descriptor(x)
+
+
+def get_sosnet_model(num_classes, backbone="resnet50", **kwargs):
+    return SoSNetWrapper(num_classes=num_classes, backbone=backbone, **kwargs)
 
 
 MODEL_REGISTRY = {

@@ -591,6 +591,79 @@ def how_asmk(x, centroids, weights):
     return out
 
 
+def sos_cov(z, hid, w3, b3, want_att=False):
+    """SoSNet's attention-weighted covariance pooling (rr_sos_cov): z [B,N,C] (or
+    NHWC [B,H,W,C]), the RAW rows of the second-order projection WITHOUT its
+    bias; hid [B,N,DH] (or NHWC), the ReLU'd second layer of the attention MLP,
+    w3 [DH] and b3 (python float) its last layer; hid None: no attention (a = 1)
+    -> (out [B, C (C + 1) / 2], the UN-normalised packed upper triangle of the
+    centred covariance of a_p z_p in torch.triu_indices order, inv_norm [B] =
+    1 / max(||out row||, 1e-12)), and att [B,N] as a third value with
+    want_att."""
+    _f32(z, "sos_cov z")
+    if z.dim() not in (3, 4):
+        raise ValueError(f"sos_cov: z [B,N,C] or [B,H,W,C], got {tuple(z.shape)}")
+    b, c = z.shape[0], z.shape[-1]
+    if c % 32 or not 32 <= c <= 512:
+        raise ValueError("sos_cov: c % 32 == 0, 32 <= c <= 512")
+    n = z.numel() // (b * c) if b else 2
+    if not 2 <= n <= 65535:
+        raise ValueError("sos_cov: 2 <= positions <= 65535 (one position: the reference divides by N - 1 = 0 and "
+                         "returns NaN)")
+    dh = 0
+    if hid is not None:
+        _f32(hid, "sos_cov hid")
+        _f32(w3, "sos_cov w3")
+        dh = hid.shape[-1]
+        if hid.dim() not in (3, 4) or hid.shape[0] != b or hid.numel() != b * n * dh or w3.numel() != dh:
+            raise ValueError(f"sos_cov: hid [B,N,DH] for z's positions and w3 [DH], got {tuple(hid.shape)} and "
+                             f"{tuple(w3.shape)}")
+        if dh % 4 or not 4 <= dh <= 512:
+            raise ValueError("sos_cov: dh % 4 == 0, 4 <= dh <= 512")
+        if hid.device != z.device or w3.device != z.device:
+            raise ValueError("sos_cov: z, hid and w3 must be on one device")
+    dev = _dev(z)
+    out = torch.empty((b, c * (c + 1) // 2), dtype=torch.float32, device=z.device)
+    inv = torch.empty((b,), dtype=torch.float32, device=z.device)
+    att = torch.empty((b, n), dtype=torch.float32, device=z.device) if want_att else None
+    if b:
+        hd = _lib.handle(dev)
+        _lib.check(_lib.lib().rr_sos_cov(hd, _ptr(z), b, n, c, _ptr(hid), dh, _ptr(w3) if hid is not None else None,
+                                         float(b3), _ptr(att), _ptr(out), _ptr(inv), _stream(dev)), hd, "rr_sos_cov")
+    return (out, inv, att) if want_att else (out, inv)
+
+
+def linear_splitk(x, w, bias, row_scale=None, act=0):
+    """y = act(row_scale[:, None] * (x @ w.T) + bias) on the split-K path
+    (rr_linear_splitk): x [M,K], w [N,K], K % 4 == 0; bias [N] and row_scale [M]
+    may be None; act 0 none, 1 ReLU, 2 QuickGELU."""
+    _f32(x, "linear_splitk x")
+    _f32(w, "linear_splitk w")
+    if x.dim() != 2 or w.dim() != 2 or w.shape[1] != x.shape[1]:
+        raise ValueError(f"linear_splitk: x [M,K] and w [N,K], got {tuple(x.shape)} and {tuple(w.shape)}")
+    m, k = x.shape
+    n = w.shape[0]
+    if k % 4 or k == 0 or n == 0:
+        raise ValueError("linear_splitk: k % 4 == 0, k > 0, n > 0")
+    if bias is not None and (_f32(bias, "linear_splitk bias").numel() != n or bias.device != x.device):
+        raise ValueError(f"linear_splitk: bias must be [{n}] on x's device")
+    if row_scale is not None and (_f32(row_scale, "linear_splitk row_scale").numel() != m or
+                                  row_scale.device != x.device):
+        raise ValueError(f"linear_splitk: row_scale must be [{m}] on x's device")
+    if int(act) not in (0, 1, 2):
+        raise ValueError("linear_splitk: act must be 0, 1 or 2")
+    dev = _dev(x)
+    if w.device != x.device:
+        raise ValueError("linear_splitk: x and w must be on one device")
+    y = torch.empty((m, n), dtype=torch.float32, device=x.device)
+    if m == 0:
+        return y
+    hd = _lib.handle(dev)
+    _lib.check(_lib.lib().rr_linear_splitk(hd, _ptr(x), m, k, _ptr(w), n, _ptr(row_scale), _ptr(bias), int(act),
+                                           _ptr(y), _stream(dev)), hd, "rr_linear_splitk")
+    return y
+
+
 def gelu(x, out=None):
     """Exact (erf) GELU (rr_gelu), elementwise; out=x runs in place."""
     _f32(x, "gelu")

@@ -405,6 +405,101 @@ def synthetic_how_head(seed, pooling, local_dim=128, num_clusters=64, num_classe
     return sd
 
 
+# ---- SoSNet head (models/sosnet.py:95-183) ----------------------------------
+SOS_ATT_KEYS = tuple(f"similarity_attention.attention_net.{i}.{k}" for i in (0, 2, 4) for k in ("weight", "bias"))
+SOS_HEAD_KEYS = ("second_order_pool.proj.weight", "second_order_pool.proj.bias", "feature_proj.0.weight",
+                 "feature_proj.0.bias", "feature_proj.3.weight", "feature_proj.3.bias", "classifier.weight",
+                 "classifier.bias")
+SOS_ATT_GAIN = 40.0  # synthetic_sos_head: the last attention layer's gain over PyTorch's default init
+
+
+def sos_head_from_state_dict(sd):
+    """The SoSNet head of a reference checkpoint (SoSNetModel's keys
+    similarity_attention.attention_net.{0,2,4}.*, second_order_pool.proj.*,
+    feature_proj.{0,3}.*, classifier.*, bare or under the wrapper's leading
+    ``backbone.``, a ``module.`` before either dropped; trunk keys are ignored)
+    as fp32 contiguous tensors:
+
+      att_w1 [H,2048], att_b1, att_w2 [H/2,H], att_b2, att_w3 [H/2], att_b3 [1]
+      (absent together: use_attention=False), proj_w [c,2048] (the 1x1 conv
+      flattened), proj_b [c], fp0_w [F, c (c + 1) / 2], fp0_b, fp3_w [F,F],
+      fp3_b, cls_w [classes,F], cls_b."""
+    flat = {}
+    for k, v in sd.items():
+        for lead in ("module.", "backbone."):
+            if k.startswith(lead):
+                k = k[len(lead):]
+        flat.setdefault(k, v)
+    missing = [k for k in SOS_HEAD_KEYS if k not in flat]
+    have_att = [k for k in SOS_ATT_KEYS if k in flat]
+    if have_att and len(have_att) != len(SOS_ATT_KEYS):
+        missing += [k for k in SOS_ATT_KEYS if k not in flat]
+    if missing:
+        raise ValueError(f"SoSNet head: missing keys {missing}")
+    pw, f0, f3, cw = (flat[k] for k in ("second_order_pool.proj.weight", "feature_proj.0.weight",
+                                        "feature_proj.3.weight", "classifier.weight"))
+    if pw.dim() != 4 or tuple(pw.shape[2:]) != (1, 1):
+        raise ValueError(f"second_order_pool.proj.weight: expected [c,Cin,1,1], got {tuple(pw.shape)}")
+    c = pw.shape[0]
+    if f0.dim() != 2 or f0.shape[1] != c * (c + 1) // 2:
+        raise ValueError(f"feature_proj.0.weight: expected [F,{c * (c + 1) // 2}], got {tuple(f0.shape)}")
+    if tuple(f3.shape) != (f0.shape[0], f0.shape[0]):
+        raise ValueError(f"feature_proj.3.weight: expected [{f0.shape[0]},{f0.shape[0]}], got {tuple(f3.shape)}")
+    if cw.dim() != 2 or cw.shape[1] != f3.shape[0]:
+        raise ValueError(f"classifier.weight: expected [classes,{f3.shape[0]}], got {tuple(cw.shape)}")
+    f = lambda a: a.float().contiguous()  # noqa: E731
+    head = {"proj_w": f(pw.reshape(c, pw.shape[1])), "proj_b": f(flat["second_order_pool.proj.bias"]),
+            "fp0_w": f(f0), "fp0_b": f(flat["feature_proj.0.bias"]), "fp3_w": f(f3),
+            "fp3_b": f(flat["feature_proj.3.bias"]), "cls_w": f(cw), "cls_b": f(flat["classifier.bias"])}
+    if have_att:
+        w1, w2, w3 = (flat[f"similarity_attention.attention_net.{i}.weight"] for i in (0, 2, 4))
+        if w1.dim() != 2 or w1.shape[1] != pw.shape[1]:
+            raise ValueError(f"similarity_attention.attention_net.0.weight: expected [H,{pw.shape[1]}], got "
+                             f"{tuple(w1.shape)}")
+        if w2.dim() != 2 or w2.shape[1] != w1.shape[0] or tuple(w3.shape) != (1, w2.shape[0]):
+            raise ValueError("similarity_attention.attention_net: expected [H/2,H] and [1,H/2] after [H,Cin], got "
+                             f"{tuple(w2.shape)} and {tuple(w3.shape)}")
+        head.update(att_w1=f(w1), att_b1=f(flat[SOS_ATT_KEYS[1]]), att_w2=f(w2), att_b2=f(flat[SOS_ATT_KEYS[3]]),
+                    att_w3=f(w3.reshape(-1)), att_b3=f(flat[SOS_ATT_KEYS[5]].reshape(1)))
+    return head
+
+
+def synthetic_sos_head(seed, second_order_dim=512, num_classes=8, use_attention=True, feature_dim=2048):
+    """Seeded SoSNet head weights under SoSNetModel's keys (SOS_ATT_KEYS with
+    use_attention, SOS_HEAD_KEYS), each Linear / Conv2d drawn as PyTorch's
+    default init, U(+-1 / sqrt(fan_in)) — except the last attention layer,
+    whose weights are drawn SOS_ATT_GAIN = 40 times wider and shifted to sum
+    to zero (its bias is not widened): with the default init a_p stays within
+    0.45-0.55 on post-ReLU maps, a constant a cancels in the L2 of the pooled
+    vector, and a head that ignored the attention would pass every test.  The
+    hidden layer is non-negative, so weights that do not sum to zero push every
+    logit one way (a within 0.0001-0.74 at one seed); zero-sum weights centre
+    the logits and a spans [<= 0.2, >= 0.8] on a 7 x 7 map."""
+    rs = np.random.RandomState(seed)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
+    sd = collections.OrderedDict()
+
+    def lin(key, out_dim, in_dim, gain=1.0, shape=None, zero_sum=False):
+        s = 1.0 / np.sqrt(in_dim)
+        w = np.empty((out_dim, in_dim), dtype=np.float32)
+        for r0 in range(0, out_dim, 256):  # row blocks: the float64 draws of the widest layer stay small
+            blk = rs.uniform(-1, 1, (min(256, out_dim - r0), in_dim)) * (s * gain)
+            w[r0:r0 + 256] = blk - blk.mean(axis=1, keepdims=True) if zero_sum else blk
+        sd[key + ".weight"] = t(w.reshape(shape) if shape else w)
+        sd[key + ".bias"] = t(rs.uniform(-1, 1, out_dim) * s)
+
+    c = second_order_dim
+    if use_attention:
+        lin("similarity_attention.attention_net.0", 512, 2048)
+        lin("similarity_attention.attention_net.2", 256, 512)
+        lin("similarity_attention.attention_net.4", 1, 256, gain=SOS_ATT_GAIN, zero_sum=True)
+    lin("second_order_pool.proj", c, 2048, shape=(c, 2048, 1, 1))
+    lin("feature_proj.0", feature_dim, c * (c + 1) // 2)
+    lin("feature_proj.3", feature_dim, feature_dim)
+    lin("classifier", num_classes, feature_dim)
+    return sd
+
+
 # ---- Token head (networks/RetrievalNet.py:94-187) ---------------------------
 _BN_KEYS =("weight", "bias", "running_mean", "running_var")
 _WB = ("weight", "bias")

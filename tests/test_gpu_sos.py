@@ -1,0 +1,459 @@
+"""SoSNet on the GPU: rr_sos_cov and rr_linear_splitk against the float64
+evaluation of tests/sos_ref.py (pinned to the reference's own output by
+tests/test_sos_host.py), and models.SoSNetWrapper end to end and head-only
+against tests/golden/sos.npz (the reference's SoSNetModel with its
+SimilarityAttention / SecondOrderPooling, make_golden_sos.py).
+
+The kernel bar, per case: max over rows of max|got - ref| / ||ref row||_2 <=
+max(1e-6, 4 e32), e32 the same quantity for the float32 torch evaluation of the
+same case (computed here and printed), as tests/test_gpu_how.py; a row is an
+image's whole output.  The descriptor bar: max(2e-6, 4 x the float32
+restatement's distance from the float64 one)."""
+import ctypes
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from research_image_retrieval_amd import _lib, models, ops
+from research_image_retrieval_amd import weights as W
+from research_image_retrieval_amd.extract import extract_vectors
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLD = os.path.join(HERE, "golden")
+sys.path.insert(0, GOLD)
+sys.path.insert(0, HERE)
+import inputs as I  # noqa: E402
+import sos_ref  # noqa: E402
+
+BAR = 1e-6
+# (b, n, c, dh; dh 0: hid = NULL): the smallest n on one diagonal tile; the 7x7
+# map; a ragged position step; c no multiple of 64 (a half-filled last tile) and
+# several chunks of one image; a wide odd c; 16 chunks; many images; the position
+# split at its widest (64 chunks); full width (131 328-wide rows, 36 tile
+# pairs); a narrow attention layer; no attention
+SHAPES = [(1, 2, 32, 256), (2, 49, 32, 256), (3, 50, 64, 256), (1, 323, 96, 256), (1, 17, 160, 256),
+          (1, 1024, 128, 256), (64, 49, 64, 256), (1, 4096, 32, 256), (2, 49, 512, 256), (2, 49, 64, 64),
+          (2, 49, 96, 0)]
+HEAD_CASES = ((2, 7, 7), (1, 5, 9), (1, 17, 19))
+
+
+def _row_err(got, ref):
+    """max over rows of max|got - ref| / ||ref row||_2"""
+    return ((got.double() - ref.double()).abs().amax(dim=-1) / ref.double().norm(dim=-1)).max().item()
+
+
+def _bits_equal(a, b):
+    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+# ---- rr_sos_cov --------------------------------------------------------------
+def _cov_case(b, n, c, dh, seed=None, offset=0.0):
+    """z ~ offset + N(0,1) x a per-row gain in [0.5, 2); hid = relu(N(0,1)); w3
+    zero-sum, scaled for logits of about +-2; per image, position 0 is planted
+    at logit +3 and position 1 at -3 (both with hid >= 0), so a spans
+    [<= 0.2, >= 0.8] at every n >= 2."""
+    rs = np.random.RandomState(1000000 * b + 1000 * n + c + dh if seed is None else seed)
+    z = offset + rs.standard_normal((b, n, c)) * rs.uniform(0.5, 2.0, (b, n, 1))
+    if not dh:
+        return torch.from_numpy(z.astype(np.float32)), None, None, 0.0
+    hid = np.maximum(rs.standard_normal((b, n, dh)), 0)
+    w3 = rs.standard_normal(dh)
+    w3 = (w3 - w3.mean()) * (2.0 / np.sqrt(0.34 * dh))
+    pos, neg = np.maximum(w3, 0), np.maximum(-w3, 0)
+    hid[:, 0] = 3.0 * pos / (pos @ pos)
+    hid[:, 1] = 3.0 * neg / (neg @ neg)
+    return (torch.from_numpy(z.astype(np.float32)), torch.from_numpy(hid.astype(np.float32)),
+            torch.from_numpy(w3.astype(np.float32)), 0.125)
+
+
+def _cov_ref(z, hid, w3, b3, dtype):
+    """(out, inv_norm, att) of rr_sos_cov in torch at dtype"""
+    att = None
+    if hid is not None:
+        att = torch.sigmoid(hid.to(dtype) @ w3.to(dtype) + b3)
+    v, inv = sos_ref.cov_from_rows(z, att, dtype)
+    return v, inv, att if att is not None else torch.ones(z.shape[:2], dtype=dtype)
+
+
+def _run_cov(z, hid, w3, b3, cuda):
+    zd = z.to(cuda)
+    hd, wd = (None, None) if hid is None else (hid.to(cuda), w3.to(cuda))
+    return (lambda zz=zd, hh=hd: ops.sos_cov(zz, hh, wd, b3, want_att=True)), zd, hd, wd
+
+
+def _check_cov(tag, z, hid, w3, b3, cuda):
+    b, n, c = z.shape
+    v64, i64, a64 = _cov_ref(z, hid, w3, b3, torch.float64)
+    v32, i32, a32 = _cov_ref(z, hid, w3, b3, torch.float32)
+    if hid is not None:
+        assert float(a64.min()) <= 0.2 and float(a64.max()) >= 0.8
+    run, zd, hd, wd = _run_cov(z, hid, w3, b3, cuda)
+    out, inv, att = run()
+    assert out.shape == (b, c * (c + 1) // 2) and inv.shape == (b,) and att.shape == (b, n)
+    again = run()
+    assert all(_bits_equal(x, y) for x, y in zip((out, inv, att), again))  # reruns
+    alone = ops.sos_cov(zd[:1].contiguous(), None if hd is None else hd[:1].contiguous(), wd, b3)
+    out, inv, att = out.cpu(), inv.cpu(), att.cpu()
+    assert bool(torch.isfinite(out).all()) and bool(torch.isfinite(inv).all()) and bool(torch.isfinite(att).all())
+    e32 = _row_err(v32, v64)
+    e32n = _row_err(v32 * i32.unsqueeze(1), v64 * i64.unsqueeze(1))
+    err = _row_err(out, v64)
+    errn = _row_err(out * inv.unsqueeze(1), v64 * i64.unsqueeze(1))
+    bar, barn = max(BAR, 4 * e32), max(BAR, 4 * e32n)
+    ea, ea32 = (att.double() - a64).abs().max().item(), (a32.double() - a64).abs().max().item()
+    e1 = max(_row_err(alone[0].cpu(), v64[:1]), _row_err(alone[0].cpu(), out[:1]))  # vs float64, vs itself in the batch
+    print(f"sos_cov {tag} ({b},{n},{c}): out {err:.3e} (float32 torch {e32:.3e}, bar {bar:.3e}); out x inv_norm "
+          f"{errn:.3e} (float32 torch {e32n:.3e}, bar {barn:.3e}); image 0 alone {e1:.3e}; att {ea:.3e} (float32 torch "
+          f"{ea32:.3e}); a in [{float(a64.min()):.3f}, {float(a64.max()):.3f}]")
+    assert ea <= max(BAR, 4 * ea32)
+    assert err <= bar and errn <= barn and e1 <= bar
+    return err, e32, bar
+
+
+@pytest.mark.parametrize("b,n,c,dh", SHAPES)
+def test_sos_cov_vs_float64(cuda, b, n, c, dh):
+    _check_cov("dh %d" % dh, *_cov_case(b, n, c, dh), cuda)
+
+
+@pytest.mark.parametrize("dh", [0, 256])
+def test_sos_cov_offset_rows_need_the_centring_first(cuda, dh):
+    """z = 50 + N(0,1): the spread is 2 % of the mean.  The bar comes from the
+    CENTRED float32 restatement; the raw-moment form E[y y^T] - mu mu^T in
+    float32 (evaluated here, printed) misses it by orders of magnitude without
+    attention, where a = 1 keeps the spread small."""
+    z, hid, w3, b3 = _cov_case(2, 49, 64, dh, seed=77, offset=50.0)
+    err, e32, bar = _check_cov("offset 50, dh %d" % dh, z, hid, w3, b3, cuda)
+    v64, _, a64 = _cov_ref(z, hid, w3, b3, torch.float64)
+    y = z * a64.float().unsqueeze(2)
+    n = y.shape[1]
+    raw = (torch.bmm(y.transpose(1, 2), y) / n - torch.einsum("bi,bj->bij", y.mean(1), y.mean(1))) * (n / (n - 1.0))
+    eraw = _row_err(sos_ref.pack(raw), v64)
+    print(f"   kernel {err:.3e}, centred float32 {e32:.3e}, raw-moment float32 {eraw:.3e}, bar {bar:.3e}")
+    if not dh:
+        assert eraw > 10 * bar
+
+
+def test_sos_cov_argument_errors(cuda):
+    L = _lib.lib()
+    hd = _lib.handle(0)
+    t = torch.zeros(65536, device=cuda)
+    out = torch.full((262144,), 7.0, device=cuda)
+    inv = torch.full((16,), 7.0, device=cuda)
+    p, po, pi = (ctypes.c_void_p(x.data_ptr()) for x in (t, out, inv))
+    p4, po4, pi4 = (ctypes.c_void_p(x.data_ptr() + 4) for x in (t, out, inv))
+
+    def call(z=p, b=1, n=4, c=64, hid=p, dh=256, w3=p, att=None, o=po, i=pi):
+        return L.rr_sos_cov(hd, z, b, n, c, hid, dh, w3, 0.0, att, o, i, None)
+
+    for kw in (dict(c=16), dict(c=48), dict(c=544), dict(c=0), dict(n=1), dict(n=0), dict(n=65536), dict(dh=6),
+               dict(dh=0), dict(dh=516), dict(b=-1), dict(z=None), dict(o=None), dict(i=None), dict(w3=None),
+               dict(z=p4), dict(hid=p4), dict(w3=p4), dict(o=po4), dict(i=pi4), dict(att=p4)):
+        assert call(**kw) == _lib.RR_EINVAL, kw
+    assert b"rr_sos_cov" in L.rr_last_error(hd)
+    assert call(b=0) == _lib.RR_OK
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all()) and bool((inv == 7.0).all())  # untouched
+    assert call(hid=None, dh=6, w3=None) == _lib.RR_OK  # no attention: dh and w3 are not read
+    torch.cuda.synchronize()
+    assert bool((inv == 7.0).sum() == 15)
+    with pytest.raises(ValueError):
+        ops.sos_cov(torch.zeros((1, 1, 64), device=cuda), None, None, 0.0)
+    got = ops.sos_cov(torch.zeros((0, 4, 64), device=cuda), None, None, 0.0)
+    assert got[0].shape == (0, 2080) and got[1].shape == (0,)
+    # all-zero rows: a zero covariance, 1 / max(0, 1e-12)
+    v, iv = ops.sos_cov(torch.zeros((1, 4, 32), device=cuda), None, None, 0.0)
+    assert float(v.abs().max()) == 0.0 and float(iv[0]) == pytest.approx(1e12, rel=1e-6)
+
+
+# ---- rr_linear_splitk --------------------------------------------------------
+# (m, k, n): one slice pair; two rows; HOW's final_proj; SoSNet's width at a
+# narrow n; k no multiple of the slice and n % 256 != 0; many rows; n % 4 != 0
+# (the core's scalar store path)
+LINEAR_SHAPES = [(1, 528, 2048), (2, 2080, 2048), (64, 8192, 2048), (3, 131328, 256), (5, 4100, 132),
+                 (1280, 8192, 64), (3, 260, 7)]
+
+
+def _row_err0(got, ref):
+    """_row_err where a reference row may be all zero (scale 0, no bias): such
+    a row must be exactly zero and is left out of the ratio."""
+    nz = ref.double().norm(dim=-1) > 0
+    assert float(got[~nz].abs().max()) == 0.0 if bool((~nz).any()) else True
+    return _row_err(got[nz], ref[nz]) if bool(nz.any()) else 0.0
+
+
+@pytest.fixture(scope="module")
+def linear_cases():
+    """(x, w, bias, row_scale) per shape, the float64 product once."""
+    out = {}
+    for m, k, n in LINEAR_SHAPES:
+        rs = np.random.RandomState(m + k + n)
+        x = torch.from_numpy(rs.standard_normal((m, k)).astype(np.float32))
+        w = torch.from_numpy((rs.standard_normal((n, k)) / np.sqrt(k)).astype(np.float32))
+        bias = torch.from_numpy(rs.standard_normal(n).astype(np.float32))
+        scale = rs.uniform(0.5, 2.0, m)
+        scale[0] = 1e12
+        if m > 1:
+            scale[m - 1] = 0.0
+        scale = torch.from_numpy(scale.astype(np.float32))
+        out[m, k, n] = (x, w, bias, scale, x.double() @ w.double().t(), F.linear(x, w))
+    return out
+
+
+@pytest.mark.parametrize("m,k,n", LINEAR_SHAPES)
+def test_linear_splitk_vs_float64(cuda, linear_cases, m, k, n):
+    x, w, bias, scale, p64, p32 = linear_cases[m, k, n]
+    xd, wd, bd, sd = (t.to(cuda) for t in (x, w, bias, scale))
+    for use_scale, use_bias, act in ((False, False, 0), (True, True, 1), (True, False, 0), (False, True, 1),
+                                     (True, True, 2)):
+        def ref(p, dt):
+            y = p * scale.to(dt).unsqueeze(1) if use_scale else p
+            y = y + bias.to(dt) if use_bias else y
+            return F.relu(y) if act == 1 else (y * torch.sigmoid(1.702 * y) if act == 2 else y)
+        r64, r32 = ref(p64, torch.float64), ref(p32, torch.float32)
+        got = ops.linear_splitk(xd, wd, bd if use_bias else None, row_scale=sd if use_scale else None, act=act)
+        assert got.shape == (m, n)
+        assert _bits_equal(got, ops.linear_splitk(xd, wd, bd if use_bias else None,
+                                                  row_scale=sd if use_scale else None, act=act))  # reruns
+        got = got.cpu()
+        assert bool(torch.isfinite(got).all())
+        err, e32 = _row_err0(got, r64), _row_err0(r32, r64)
+        bar = max(BAR, 4 * e32)
+        print(f"linear_splitk ({m},{k},{n}) scale {use_scale} bias {use_bias} act {act}: {err:.3e} of the row norm "
+              f"(float32 torch {e32:.3e}, bar {bar:.3e})")
+        assert err <= bar
+    if (m, k, n) == (2, 2080, 2048):  # no scale, no activation: rr_linear's product to the same bar
+        lin = ops.linear(xd, wd, bd).cpu()
+        assert _row_err(lin, p64 + bias.double()) <= max(BAR, 4 * _row_err(p32 + bias, p64 + bias.double()))
+
+
+def test_linear_splitk_argument_errors(cuda):
+    L = _lib.lib()
+    hd = _lib.handle(0)
+    t = torch.zeros(4096, device=cuda)
+    y = torch.full((64,), 7.0, device=cuda)
+    p, py = ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(y.data_ptr())
+    p4 = ctypes.c_void_p(t.data_ptr() + 4)
+
+    def call(x=p, m=2, k=64, w=p, n=8, act=0, out=py):
+        return L.rr_linear_splitk(hd, x, m, k, w, n, None, None, act, out, None)
+
+    for kw in (dict(k=6), dict(k=0), dict(n=0), dict(m=-1), dict(x=None), dict(w=None), dict(out=None), dict(x=p4),
+               dict(w=p4), dict(act=3), dict(act=-1)):
+        assert call(**kw) == _lib.RR_EINVAL, kw
+    assert b"rr_linear_splitk" in L.rr_last_error(hd)
+    assert call(m=0) == _lib.RR_OK
+    torch.cuda.synchronize()
+    assert bool((y == 7.0).all())
+    assert ops.linear_splitk(torch.zeros((0, 8), device=cuda), torch.zeros((3, 8), device=cuda), None).shape == (0, 3)
+
+
+# ---- the per-stream scratch ---------------------------------------------------
+@pytest.mark.parametrize("cov_first", [True, False])
+def test_two_streams_do_not_share_the_scratch(cuda, cov_first):
+    """rr_sos_cov at (1, 200, 64) (4 chunks through the scratch) on one stream
+    and rr_linear_splitk at (2, 2080, 256) on another, enqueued in either order:
+    each result is the bits of the same call alone on the default stream; then
+    both on one stream, in both orders."""
+    z, hid, w3, b3 = _cov_case(1, 200, 64, 256)
+    run_c, _, _, _ = _run_cov(z, hid, w3, b3, cuda)
+    rs = np.random.RandomState(9)
+    xd = torch.from_numpy(rs.standard_normal((2, 2080)).astype(np.float32)).to(cuda)
+    wd = torch.from_numpy(rs.standard_normal((256, 2080)).astype(np.float32)).to(cuda)
+    run_l = lambda: ops.linear_splitk(xd, wd, None)  # noqa: E731
+    alone_c, alone_l = run_c(), run_l()
+    torch.cuda.synchronize(cuda)
+    sc, sl = torch.cuda.Stream(cuda), torch.cuda.Stream(cuda)
+    got = {}
+    order = (("c", run_c, sc), ("l", run_l, sl))
+    for name, run, s in (order if cov_first else order[::-1]):
+        with torch.cuda.stream(s):
+            got[name] = run()
+    sc.synchronize()
+    sl.synchronize()
+    assert all(_bits_equal(a, b) for a, b in zip(got["c"], alone_c)) and _bits_equal(got["l"], alone_l)
+    one = [run() for _, run, _ in (order if cov_first else order[::-1])]
+    torch.cuda.synchronize(cuda)
+    c1, l1 = (one[0], one[1]) if cov_first else (one[1], one[0])
+    assert all(_bits_equal(a, b) for a, b in zip(c1, alone_c)) and _bits_equal(l1, alone_l)
+
+
+# ---- models.SoSNetWrapper -----------------------------------------------------
+@pytest.fixture(scope="module")
+def fx():
+    return np.load(os.path.join(GOLD, "sos.npz"))
+
+
+@pytest.fixture(scope="module")
+def head(fx):
+    return W.sos_head_from_state_dict(W.synthetic_sos_head(int(fx["head_seed"]), int(fx["second_order_dim"]), 8))
+
+
+@pytest.fixture(scope="module")
+def nets(fx):
+    """One wrapper per conv core over one reference-shaped checkpoint: the
+    trunk under the wrapper's backbone.backbone.{0..7} nn.Sequential indices,
+    the head under backbone."""
+    inv = {"conv1": "0", "bn1": "1", "layer1": "4", "layer2": "5", "layer3": "6", "layer4": "7"}
+    sd = {}
+    for key, v in W.synthetic_resnet_state_dict("resnet101", int(fx["weight_seed"])).items():
+        first, rest = key.split(".", 1)
+        sd[f"backbone.backbone.{inv[first]}.{rest}"] = v
+    c = int(fx["second_order_dim"])
+    sd.update({"backbone." + key: v for key, v in W.synthetic_sos_head(int(fx["head_seed"]), c, 8).items()})
+    made = {}
+
+    def get(conv_math):
+        if conv_math not in made:
+            made[conv_math] = models.SoSNetWrapper(8, backbone="resnet101", second_order_dim=c, state_dict=sd,
+                                                   device="cuda:0", conv_math=conv_math)
+        return made[conv_math]
+    return get
+
+
+@pytest.fixture(scope="module")
+def head_refs(head):
+    """float64 and float32 literal restatements of the head-only cases, computed once."""
+    out = {}
+    for c in HEAD_CASES:
+        x = torch.from_numpy(I.feature_map(12000 + c[1] * c[2], c[0], 2048, c[1], c[2]))
+        out[c] = (x, sos_ref.head_forward(x, head, torch.float64), sos_ref.head_forward(x, head, torch.float32))
+    return out
+
+
+@pytest.mark.parametrize("case", HEAD_CASES)
+def test_sos_head_vs_reference(cuda, fx, nets, head_refs, case):
+    """attention -> covariance pooling -> feature_proj -> F.normalize alone on
+    maps where every piece matters (test_sos_host.py: each degenerate piece
+    moves these descriptors by >= 100 x the bar).  Measured on the MI355X: see
+    DESIGN.md, "SoSNet head"."""
+    b, h, w = case
+    tag = f"head_b{b}_{h}x{w}"
+    x4, r64, r32 = head_refs[case]
+    d32 = (r32["out"].double() - r64["out"]).abs().max().item()
+    bar = max(2e-6, 4 * d32)
+    x = x4.permute(0, 2, 3, 1).contiguous().to(cuda)
+    for cm in ("f32", "h2"):
+        net = nets(cm).backbone
+        taps = {}
+        f = net.head(x, taps=taps)
+        got = ops.l2_normalize(f, 1e-12).cpu()
+        err = np.abs(got.numpy() - fx[tag + "_out"]).max()
+        e64 = (got.double() - r64["out"]).abs().max().item()
+        print(f"SoSNet {tag} {cm}: descriptor max|err| vs the reference {err:.3e}, vs float64 {e64:.3e}; float32 "
+              f"restatement vs float64 {d32:.3e}; bar {bar:.3e}")
+        taps["vhat"] = taps["cov"] * taps["inv_norm"].unsqueeze(1)
+        rows = {}
+        for key in ("att", "cov", "vhat", "hidden", "features"):
+            e32k = _row_err(r32[key], r64[key])
+            rows[key] = (_row_err(taps[key].cpu(), r64[key]), max(BAR, 4 * e32k))
+            stored = f"{tag}_{key}"
+            if stored in fx.files:
+                es = _row_err(taps[key].cpu(), torch.from_numpy(fx[stored]))
+                print(f"   {key}: vs the stored reference {es:.3e}, vs float64 {rows[key][0]:.3e}, bar {rows[key][1]:.3e}")
+                assert es <= rows[key][1], key
+            else:
+                print(f"   {key}: vs float64 {rows[key][0]:.3e}, bar {rows[key][1]:.3e}")
+        assert got.shape == (b, 2048)
+        assert err <= bar
+        if case == (1, 5, 9):
+            for key, (e, kb) in rows.items():
+                assert e <= kb, key
+
+
+@pytest.mark.parametrize("tag", ["b2_224", "b1_odd"])
+def test_sos_vs_reference(cuda, fx, nets, head, tag):
+    """End to end.  The model's descriptor against the float64 restatement on
+    the GPU trunk's OWN x4, at the head bar; its distance to the stored
+    reference descriptor is printed and bounded by the triangle inequality:
+    the head bar + max|ref64(x4 gpu) - ref64(x4 fixture)| + max|ref64(x4
+    fixture) - stored|, all three computed here (the trunk's own error,
+    amplified by the centring, gets no invented number)."""
+    tr = np.load(os.path.join(GOLD, "resnet_dolg_v15.npz"))
+    seed, b, h, w = (int(v) for v in fx[tag + "_case"])
+    stored = torch.from_numpy(fx[tag + "_out"]).double()
+    f64_fix = sos_ref.head_forward(torch.from_numpy(tr[tag + "_x4"]), head, torch.float64)["out"]
+    t_fix = (f64_fix - stored).abs().max().item()
+    for cm in ("f32", "h2"):
+        net = nets(cm).backbone
+        x = net._input(I.trunk_input(seed, b, h, w).to(cuda))
+        x4, x4a = net._trunk(x)
+        got = ops.l2_normalize(net.head(x4, x4a), 1e-12).cpu().double()
+        x4c = x4.permute(0, 3, 1, 2).contiguous().cpu()
+        r64, r32 = sos_ref.head_forward(x4c, head, torch.float64), sos_ref.head_forward(x4c, head, torch.float32)
+        bar = max(2e-6, 4 * (r32["out"].double() - r64["out"]).abs().max().item())
+        e_head = (got - r64["out"]).abs().max().item()
+        t_trunk = (r64["out"] - f64_fix).abs().max().item()
+        dist = (got - stored).abs().max().item()
+        print(f"SoSNet {tag} {cm}: descriptor vs float64 on the GPU trunk's x4 {e_head:.3e} (bar {bar:.3e}); distance "
+              f"to the stored reference {dist:.3e} <= {bar:.3e} + {t_trunk:.3e} (trunk) + {t_fix:.3e} (fixture)")
+        assert got.shape == (b, 2048) == (b, nets(cm).outputdim)
+        assert _bits_equal(nets(cm).extract_global_descriptor(I.trunk_input(seed, b, h, w).to(cuda)).cpu(),
+                           got.float())
+        assert e_head <= bar
+        assert dist <= bar + t_trunk + t_fix
+
+
+def test_sos_entry_points_agree(cuda, nets):
+    """forward_test == forward_test_u8 == extract_vectors (batches of 2,
+    multi-scale) on 4 images of 96 x 128; forward's logits have their shape."""
+    net = nets("h2")
+    rs = np.random.RandomState(17)
+    imgs = torch.from_numpy(rs.randint(0, 256, size=(4, 96, 128, 3), dtype=np.uint8))
+    x = ops.preprocess_u8(imgs.to(cuda))
+    xn = x.permute(0, 3, 1, 2).contiguous()
+    a = net.forward_test(xn)
+    assert a.shape == (4, 2048)
+    assert bool(((a.double().norm(dim=1) - 1.0).abs() < 1e-5).all())
+    assert _bits_equal(a, net.forward_test_u8(imgs.to(cuda)))
+    assert _bits_equal(a, net.extract_global_descriptor(xn)) and _bits_equal(a, net.extract_descriptor(xn))
+    assert _bits_equal(extract_vectors(net, [imgs[:2], imgs[2:]], ms=[1], device=cuda, print_freq=0).to(cuda),
+                       torch.cat([net.forward_test_u8(imgs[:2].to(cuda)), net.forward_test_u8(imgs[2:].to(cuda))]))
+    ms = [1, 2 ** -0.5, 0.5]
+    got = extract_vectors(net, [imgs[:2], imgs[2:]], ms=ms, device=cuda, print_freq=0)
+    parts = []
+    for batch in (imgs[:2], imgs[2:]):
+        xb = ops.preprocess_u8(batch.to(cuda))
+        acc = None
+        for s in ms:
+            xs = xb if s == 1 else ops.resize_bilinear(xb, int(96 * s), int(128 * s), scale_factor=s)
+            f = net.forward_test_nhwc(xs)
+            acc = f.clone() if acc is None else acc.add_(f)
+        acc.div_(len(ms))
+        parts.append(ops.l2_normalize(acc, 1e-12).cpu())
+    assert got.shape == (4, 2048)
+    assert _bits_equal(got.cpu(), torch.cat(parts))
+    none, logits = net(xn)
+    assert none is None and logits.shape == (4, 8) and bool(torch.isfinite(logits).all())
+    feats = net.extract_features(xn)
+    assert _bits_equal(ops.l2_normalize(feats, 1e-12), a)
+    with pytest.raises(ValueError, match="NaN"):  # a 1 x 1 map
+        net.backbone.head(torch.zeros((1, 1, 1, 2048), device=cuda))
+
+
+@pytest.mark.parametrize("use_attention,c", [(False, 32), (True, 64)])
+def test_sos_other_heads_match_the_restatement(cuda, use_attention, c):
+    """use_attention=False, and second_order_dim = 64, on a 5 x 9 map, head only, both cores."""
+    x4 = torch.from_numpy(I.feature_map(12045, 1, 2048, 5, 9))
+    x = x4.permute(0, 2, 3, 1).contiguous().to(cuda)
+    head = W.sos_head_from_state_dict(W.synthetic_sos_head(22, c, 8, use_attention))
+    r64, r32 = sos_ref.head_forward(x4, head, torch.float64), sos_ref.head_forward(x4, head, torch.float32)
+    bar = max(2e-6, 4 * (r32["out"].double() - r64["out"]).abs().max().item())
+    for cm in ("f32", "h2"):
+        net = models.get_sosnet_model(8, backbone="resnet50", second_order_dim=c, use_attention=use_attention, seed=21,
+                                      device="cuda:0", conv_math=cm)
+        assert isinstance(net, models.SoSNetWrapper) and net.backbone.backbone.name == "resnet50"
+        assert all(torch.equal(net.backbone.w[key].cpu(), head[key]) for key in head if key != "att_b3")
+        taps = {}
+        got = ops.l2_normalize(net.backbone.head(x, taps=taps), 1e-12).cpu()
+        err = (got.double() - r64["out"]).abs().max().item()
+        print(f"SoSNet attention {use_attention}, second_order_dim {c}, {cm}: descriptor vs float64 {err:.3e}; bar "
+              f"{bar:.3e}")
+        assert got.shape == (1, 2048) and err <= bar
+        assert taps["cov"].shape == (1, c * (c + 1) // 2)
+        if not use_attention:
+            assert bool((taps["att"] == 1.0).all())
