@@ -71,7 +71,9 @@ typedef struct rr_handle_s* rr_handle_t;
  * revision-7 header still passes the right arguments everywhere; likewise
  * rr_attention_hd128, rr_token_pool and rr_gelu (the Token head), and
  * rr_how_vlad and rr_how_asmk (the HOW head's aggregations), rr_sos_cov and
- * rr_linear_splitk (the SoSNet head: added, no existing entry changed), and the native
+ * rr_linear_splitk (the SoSNet head: added, no existing entry changed),
+ * rr_cls_attn_pool and rr_linear_splitk_ex (the token aggregator's folded last
+ * layer: added, no existing entry changed), and the native
  * trunk plan's rr_trunk_h2_* entries, rr_timing_collect_ex and the tuning key
  * RR_TUNE_TRUNK_PARTS (16); rr_timing_collect keeps its arguments and now
  * returns the UNION of the class's launch intervals (equal to the former sum
@@ -777,6 +779,41 @@ int rr_sos_cov(rr_handle_t h, const float* z, int b, int n, int c,
 int rr_linear_splitk(rr_handle_t h, const float* x, int m, int k,
                      const float* w, int n, const float* row_scale,
                      const float* bias, int act, float* y, void* stream);
+
+/* Same with a residual, as rr_linear_ex has one:
+ *   y[i][:] = act(row_scale[i] * (x_i . w^T) + bias + residual[i][:]),
+ * residual [m][n] dense, may be NULL (then the same bits as rr_linear_splitk:
+ * both run the same kernels).  For the token aggregator's folded last layer,
+ * whose B-row linears at K = 4096 and K = 2048 sit at rr_linear_ex's K-set
+ * floor.                                                                     */
+int rr_linear_splitk_ex(rr_handle_t h, const float* x, int m, int k,
+                        const float* w, int n, const float* row_scale,
+                        const float* bias, const float* residual, int act,
+                        float* y, void* stream);
+
+/* ---- token aggregator (models/token_based.py:60-86) ---------------------- */
+/* The attention of the encoder's LAST layer for the global token alone
+ * (TokenAggregator.forward keeps x[0], :81), with the K and V projections
+ * folded away.  x [b][seq][d] dense: the layer's input rows; qt [b][heads][d]:
+ * the folded, scaled query q~_h = Wk_h^T (Wq_h x0 + bq_h) / sqrt(d / heads)
+ * (one rr_linear on b rows; the key bias shifts every score of a head alike and
+ * cancels in the softmax); per image and head
+ *   p_hj = softmax_j(qt_h . x_j)         (the maximum subtracted before exp)
+ *   out_h = sum_j p_hj x_j               [b][heads][d]
+ * and the caller applies M = [Wo[:,h] Wv_h]_h to out (rr_linear_splitk_ex with
+ * the residual).  p (may be NULL) receives [b][heads][seq].
+ * One workgroup per image takes all heads: x leaves HBM once, the second pass
+ * reads it from cache; scores, p and the partial sums stay in LDS.  No float
+ * atomics and no scratch: every sum runs in an order fixed by (seq, d, heads)
+ * alone, so an image's result is the same bits alone or in a batch, on every
+ * run and on every stream.
+ * d % 64 == 0, 64 <= d <= 1024; 1 <= heads <= 16; 1 <= seq <= 256
+ * (rr_attention's limit); x, qt, out and p 16-B aligned (else RR_EINVAL,
+ * nothing written); b == 0 is RR_OK and launches nothing; offsets are 64-bit.
+ * Timing class 5.                                                           */
+int rr_cls_attn_pool(rr_handle_t h, const float* x, int b, int seq, int d,
+                     const float* qt, int heads, float* p, float* out,
+                     void* stream);
 
 /* ---- native ResNet trunk plan (f16x2 core) -------------------------------
  * One call per forward for the whole bottleneck-ResNet trunk (torchvision

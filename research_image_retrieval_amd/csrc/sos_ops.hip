@@ -1,6 +1,7 @@
 // sos_ops.hip — the SoSNet head's kernels (gfx950): the attention-weighted,
 // centred covariance of the projected rows as its packed upper triangle, and
-// the split-K form of the skinny linear that follows it.
+// the split-K form of the skinny linear that follows it (rr_linear_splitk; with a
+// residual, rr_linear_splitk_ex, for the token aggregator's folded last layer).
 //
 // Reference (models/sosnet.py): SimilarityAttention.forward :76-92 (the last
 // Linear + Sigmoid and the multiply), SecondOrderPooling.forward :27-55 (mean,
@@ -273,11 +274,12 @@ __global__ __launch_bounds__(256) void sos_inv_norm_kernel(const float* __restri
   inv_norm[img] = 1.f / fmaxf(sqrtf(s), kSosEps);
 }
 
-// y[i][j] = act(row_scale[i] * sum_s part[i][s][j] + bias[j]), the slices added
-// in index order; one thread per output
+// y[i][j] = act(row_scale[i] * sum_s part[i][s][j] + bias[j] + residual[i][j]),
+// the slices added in index order; one thread per output
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, int splits, int n,
                                                             long long total, const float* __restrict__ row_scale,
-                                                            const float* __restrict__ bias, int act,
+                                                            const float* __restrict__ bias,
+                                                            const float* __restrict__ residual, int act,
                                                             float* __restrict__ y) {
   const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
   if (e >= total) return;
@@ -289,6 +291,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   for (int s = 0; s < splits; ++s) t += pp[(long long)s * n];
   if (row_scale != nullptr) t *= row_scale[i];
   if (bias != nullptr) t += bias[j];
+  if (residual != nullptr) t += residual[e];
   if (act == 1) t = fmaxf(t, 0.f);
   else if (act == 2) t = t / (1.f + expf(-1.702f * t));  // QuickGELU, x sigmoid(1.702 x)
   y[e] = t;
@@ -361,20 +364,21 @@ extern "C" int rr_sos_cov(rr_handle_t h, const float* z, int b, int n, int c, co
   return check_hip(h, hipGetLastError(), "sos_cov launch");
 }
 
-extern "C" int rr_linear_splitk(rr_handle_t h, const float* x, int m, int k, const float* w, int n,
-                                const float* row_scale, const float* bias, int act, float* y, void* stream) {
-  RR_ENTRY(h);
+// rr_linear_splitk and rr_linear_splitk_ex (residual == nullptr: the former)
+static int linear_splitk(rr_handle_t h, const char* who, const float* x, int m, int k, const float* w, int n,
+                         const float* row_scale, const float* bias, const float* residual, int act, float* y,
+                         void* stream) {
   if (!x || !w || !y || m < 0 || k <= 0 || n <= 0 || (k & 3) || act < 0 || act > 2)
-    return set_error(h, RR_EINVAL, "rr_linear_splitk: bad argument (k % 4 == 0, act 0, 1 or 2)");
+    return set_error(h, RR_EINVAL, std::string(who) + ": bad argument (k % 4 == 0, act 0, 1 or 2)");
   if (((uintptr_t)x & 15) || ((uintptr_t)w & 15))
-    return set_error(h, RR_EINVAL, "rr_linear_splitk: x/w must be 16-byte aligned");
+    return set_error(h, RR_EINVAL, std::string(who) + ": x/w must be 16-byte aligned");
   if (m == 0) return RR_OK;
   const auto [splits, k_split] = splitk_plan(m, k, n, device_cu_count(h));
   const long long total = (long long)m * n;
-  if ((total + 255) / 256 > 0x7fffffffLL) return set_error(h, RR_EINVAL, "rr_linear_splitk: too many outputs");
+  if ((total + 255) / 256 > 0x7fffffffLL) return set_error(h, RR_EINVAL, std::string(who) + ": too many outputs");
   hipStream_t s = (hipStream_t)stream;
   void* p = nullptr;
-  if (int rc = stream_scratch(h, s, (size_t)total * splits * sizeof(float), &p, "rr_linear_splitk")) return rc;
+  if (int rc = stream_scratch(h, s, (size_t)total * splits * sizeof(float), &p, who)) return rc;
   GemmArgs g;
   g.A = x;
   g.lda = k;
@@ -390,6 +394,19 @@ extern "C" int rr_linear_splitk(rr_handle_t h, const float* x, int m, int k, con
   if (int rc = launch_gemm(h, A_DENSE, E_STORE, g, s, kTimeGemm)) return rc;
   TimedLaunch tl(h, kTimeGemm, s);
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)p,
-                     splits, n, total, row_scale, bias, act, y);
+                     splits, n, total, row_scale, bias, residual, act, y);
   return check_hip(h, hipGetLastError(), "splitk_reduce launch");
+}
+
+extern "C" int rr_linear_splitk(rr_handle_t h, const float* x, int m, int k, const float* w, int n,
+                                const float* row_scale, const float* bias, int act, float* y, void* stream) {
+  RR_ENTRY(h);
+  return linear_splitk(h, "rr_linear_splitk", x, m, k, w, n, row_scale, bias, nullptr, act, y, stream);
+}
+
+extern "C" int rr_linear_splitk_ex(rr_handle_t h, const float* x, int m, int k, const float* w, int n,
+                                   const float* row_scale, const float* bias, const float* residual, int act,
+                                   float* y, void* stream) {
+  RR_ENTRY(h);
+  return linear_splitk(h, "rr_linear_splitk_ex", x, m, k, w, n, row_scale, bias, residual, act, y, stream);
 }

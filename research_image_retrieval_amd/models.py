@@ -11,6 +11,10 @@ SoSNet (models/sosnet.py:95-212) is built with ``get_sosnet_model(num_classes,
 backbone=..., second_order_dim=...)`` or ``SoSNetWrapper``; its registry names
 are NOT registered yet: ``get_model('sosnet_r50' | 'sosnet_r101', ...)`` still
 raises NotImplementedError (the names stay in OUT_OF_SCOPE).
+The token aggregator (models/token_based.py:13-212) likewise: ``get_token_model(
+num_classes, backbone=..., hidden_dim=..., num_heads=..., num_layers=...)`` or
+``TokenWrapper``, inputs up to 448 x 448 (196 positions); ``get_model('token_r50'
+| 'token_r101', ...)`` still raises NotImplementedError.
 Training (``forward(x, targets)`` losses, optimizers) is out of scope
 (SURVEY.md §2 row 13): ``forward`` only produces eval-mode logits.
 """
@@ -444,6 +448,218 @@ class SoSNetWrapper(_Extractor):
 
 def get_sosnet_model(num_classes, backbone="resnet50", **kwargs):
     return SoSNetWrapper(num_classes=num_classes, backbone=backbone, **kwargs)
+
+
+class TokenModel(_Extractor):
+    """models/token_based.py:89-159, eval mode: resnet trunk -> TokenAggregator
+    (:35-86: input_proj Linear(2048, hidden_dim) per position, + the sinusoidal
+    pe[i], the learnable global token in front, a post-norm nn.TransformerEncoder
+    of num_layers layers (ReLU, FFN width 4 hidden_dim, LN eps 1e-5, no final
+    norm), row 0, output_proj back to 2048) -> feature_proj Linear(2048,
+    feature_dim); extract_descriptor adds F.normalize.  (networks.Token is the
+    OTHER token model, networks/RetrievalNet.py's Token_Refine.)
+
+    Launches after the trunk: input_proj as a 1x1 conv (conv_math "h2": the
+    f16x2 core on the trunk's max-|x| record; "f32": rr_conv2d); rr_vit_tokens
+    with cls = the global token and a position table whose row 0 is zero and
+    row 1 + i is pe[i]; per layer but the last rr_linear_ex (QKV), rr_attention,
+    rr_linear_ex (+ residual), rr_layernorm, rr_linear_ex (ReLU), rr_linear_ex
+    (+ residual), rr_layernorm over all B (1 + N) rows.  Only row 0 of the last
+    layer is used (:81), so that layer runs on B rows with its K and V
+    projections folded into two host-side products (weights.
+    tokagg_fold_last_layer; 2 heads hidden_dim^2 floats, 16 MB at the defaults):
+    rr_linear (q~ = A x0 + a0), rr_cls_attn_pool (one pass over the layer's input),
+    rr_linear_splitk_ex (M, + m0, + x0), rr_layernorm, rr_linear_ex (ReLU),
+    rr_linear_splitk_ex (+ residual), rr_layernorm; then rr_linear x 2 and
+    rr_l2_normalize.  (The two split-K launches have K = heads hidden_dim and
+    4 hidden_dim on B rows: through rr_linear_ex, one workgroup per output tile
+    walking all of K, the folded layer measured SLOWER than the unfolded one.)  The
+    global token's rows are gathered for the B-row launches by one strided
+    device copy.  head(..., fold_last=False) runs the last layer like the others
+    and takes row 0: the cross-check and the timing baseline, never the default.
+
+    Constructor: the reference's (backbone, pretrained, num_classes,
+    feature_dim, hidden_dim, num_heads, num_layers), then state_dict (trunk keys
+    as networks.ResNet accepts, the reference's index-named nn.Sequential keys
+    included; head keys as weights.tokagg_head_from_state_dict), seed (synthetic
+    weights when state_dict is None), device, conv_math and stride_on as
+    GeMModel.  hidden_dim % 64 == 0 in 64..1024, 1 <= num_heads <= 16 dividing it
+    (rr_cls_attn_pool), hidden_dim == 64 num_heads when num_layers > 1
+    (rr_attention), num_layers >= 1.  The reference's pe buffer has max_len = 196
+    rows and its broadcast raises on more positions, so inputs go up to 448 x 448.
+
+    get_model("token_r50" | "token_r101") still raises NotImplementedError:
+    the names stay in OUT_OF_SCOPE and out of MODEL_REGISTRY (build the model
+    with get_token_model)."""
+
+    in_channels = 4
+
+    def __init__(self, backbone="resnet50", pretrained=False, num_classes=1000, feature_dim=2048, hidden_dim=512,
+                 num_heads=8, num_layers=2, state_dict=None, seed=0, device="cuda", conv_math="h2", stride_on="3x3"):
+        if pretrained:
+            raise ValueError("pretrained weights need a download; pass a local state_dict instead "
+                             "(models/token_based.py:92 defaults to pretrained=True)")
+        if backbone not in ("resnet50", "resnet101"):
+            raise ValueError(f"Unsupported backbone: {backbone}")
+        d, nh = hidden_dim, num_heads
+        if d % 64 or not 64 <= d <= 1024:
+            raise ValueError("TokenModel: hidden_dim % 64 == 0, 64 <= hidden_dim <= 1024 (rr_cls_attn_pool)")
+        if not 1 <= nh <= 16 or d % nh:
+            raise ValueError("TokenModel: 1 <= num_heads <= 16, num_heads dividing hidden_dim (rr_cls_attn_pool)")
+        if num_layers < 1:
+            raise ValueError("TokenModel: num_layers >= 1")
+        if num_layers > 1 and d != 64 * nh:
+            raise ValueError("TokenModel: hidden_dim == 64 num_heads when num_layers > 1 (rr_attention's head width)")
+        if state_dict is None:
+            head = W.tokagg_head_from_state_dict(W.synthetic_tokagg_head(seed + 1, d, nh, num_layers, num_classes,
+                                                                         feature_dim))
+        else:
+            head = W.tokagg_head_from_state_dict(state_dict)
+        if head["in_w"].shape[0] != d or W.tokagg_num_layers(head) != num_layers or \
+                head["fp_w"].shape[0] != feature_dim:
+            raise ValueError("TokenModel: head weight shapes do not fit hidden_dim, num_layers and feature_dim")
+        a, a0, m, m0 = W.tokagg_fold_last_layer(W.tokagg_layer(head, num_layers - 1), nh)
+        pos = torch.cat([torch.zeros(1, d), head.pop("pe")]).contiguous()  # row 0: the global token gets no term
+        self.max_len = pos.shape[0] - 1
+        self.device = torch.device(device)
+        self.conv_math = conv_math
+        self.backbone = ResNet(backbone, state_dict, seed, device, conv_math=conv_math, stride_on=stride_on)
+        if head["in_w"].shape[1] != self.backbone.outputdim_block5:
+            raise ValueError("TokenModel: token_aggregator.input_proj does not fit the trunk")
+        self.w = {k: v.to(self.device) for k, v in head.items()}
+        self.w.update(pos=pos.to(self.device), fold_a=a.to(self.device), fold_a0=a0.to(self.device),
+                      fold_m=m.to(self.device), fold_m0=m0.to(self.device))
+        self.in_w = self.w["in_w"].view(d, 1, 1, -1)
+        self.in_h2 = ops.H2Conv(self.in_w) if conv_math == "h2" else None
+        self.hidden_dim, self.num_heads, self.num_layers, self.feature_dim = d, nh, num_layers, feature_dim
+        self.outputdim = feature_dim
+
+    def _full_layer(self, x, i, b, seq):
+        """Encoder layer i on all rows x [b seq, d] (nn.TransformerEncoderLayer, post-norm)."""
+        w = self.w
+        qkv = ops.linear_ex(x, w[f"l{i}_qkv_w"], w[f"l{i}_qkv_b"])
+        att = ops.attention(qkv, b, seq, self.num_heads, self.hidden_dim // self.num_heads)
+        y = ops.linear_ex(att, w[f"l{i}_out_w"], w[f"l{i}_out_b"], residual=x)
+        return self._ffn(ops.layernorm(y, w[f"l{i}_n1_g"], w[f"l{i}_n1_b"], 1e-5), i)
+
+    def _ffn(self, y, i, few_rows=False):
+        """linear1, ReLU, linear2, + residual, norm2.  few_rows (the folded layer's B
+        rows): linear2, K = 4 hidden_dim, on the split-K path."""
+        w = self.w
+        hid = ops.linear_ex(y, w[f"l{i}_l1_w"], w[f"l{i}_l1_b"], act=1)
+        if few_rows:
+            z = ops.linear_splitk(hid, w[f"l{i}_l2_w"], w[f"l{i}_l2_b"], residual=y)
+        else:
+            z = ops.linear_ex(hid, w[f"l{i}_l2_w"], w[f"l{i}_l2_b"], residual=y)
+        return ops.layernorm(z, w[f"l{i}_n2_g"], w[f"l{i}_n2_b"], 1e-5)
+
+    def _folded_last_layer(self, x, b, seq, taps):
+        """Row 0 of the last layer's output from its input x [b seq, d]: [b, d]."""
+        w, d, nh, i = self.w, self.hidden_dim, self.num_heads, self.num_layers - 1
+        x3 = x.view(b, seq, d)
+        x0 = x3[:, 0].contiguous()
+        qt = ops.linear(x0, w["fold_a"], w["fold_a0"]).view(b, nh, d)
+        got = ops.cls_attn_pool(x3, qt, want_p=taps is not None)
+        pooled = got[0] if taps is not None else got
+        if taps is not None:
+            taps.update(p=got[1], pooled=pooled)
+        y = ops.linear_splitk(pooled.view(b, nh * d), w["fold_m"], w["fold_m0"], residual=x0)
+        return self._ffn(ops.layernorm(y, w[f"l{i}_n1_g"], w[f"l{i}_n1_b"], 1e-5), i, few_rows=True)
+
+    def head(self, x4, x4_amax=None, taps=None, fold_last=True):
+        """x4 NHWC -> features [B,feature_dim] (:126-137).  taps: a dict that
+        receives tokens [B,1+N,d], layer_out (the last layer's input), p
+        [B,heads,1+N] and pooled [B,heads,d] (fold_last only), agg [B,2048] and
+        features (tests).  fold_last=False: the last layer over all rows with
+        the other layers' kernels, row 0 taken afterwards."""
+        b, n, d = x4.shape[0], x4.shape[1] * x4.shape[2], self.hidden_dim
+        if n > self.max_len:
+            raise ValueError(f"TokenModel: {n} positions exceed the positional encoding's max_len = {self.max_len} "
+                             "(models/token_based.py:16, :32: the reference's broadcast raises; inputs up to 448 x 448)")
+        seq = 1 + n
+        if self.conv_math == "h2":
+            if x4_amax is None:
+                x4_amax = ops.amax_f32(x4, ops.amax_records(1, x4.device)[0])
+            y = ops.conv2d_h2(x4, x4_amax, self.in_h2, self.w["in_b"], 1, 0, None, False)
+        else:
+            y = ops.conv2d(x4, self.in_w, self.w["in_b"], 1, 0, None, False)
+        x = ops.vit_tokens(y.view(b * n, d), b, self.w["global_token"], self.w["pos"])
+        if taps is not None:
+            taps["tokens"] = x.view(b, seq, d)
+        for i in range(self.num_layers - 1):
+            x = self._full_layer(x, i, b, seq)
+        if taps is not None:
+            taps["layer_out"] = x.view(b, seq, d)
+        if fold_last:
+            g = self._folded_last_layer(x, b, seq, taps)
+        else:
+            g = self._full_layer(x, self.num_layers - 1, b, seq).view(b, seq, d)[:, 0].contiguous()
+        agg = ops.linear(g, self.w["op_w"], self.w["op_b"])
+        f = ops.linear(agg, self.w["fp_w"], self.w["fp_b"])
+        if taps is not None:
+            taps.update(agg=agg, features=f)
+        return f
+
+    def _trunk(self, x_nhwc, hook=None):
+        if self.conv_math == "h2":
+            return self.backbone(x_nhwc, hook=hook, return_amax=True)
+        return self.backbone(x_nhwc), None
+
+    def extract_features_nhwc(self, x_nhwc, hook=None):
+        return self.head(*self._trunk(x_nhwc, hook))
+
+    @torch.no_grad()
+    def extract_features(self, x):
+        return self.extract_features_nhwc(self._input(x))
+
+    def forward_test_nhwc(self, x_nhwc, hook=None):
+        f = self.extract_features_nhwc(x_nhwc, hook)
+        return ops.l2_normalize(f, EPS_L2, out=f)
+
+    @torch.no_grad()
+    def extract_descriptor(self, x):
+        return self.forward_test(x)
+
+    @torch.no_grad()
+    def forward(self, x, targets=None):
+        feats = self.extract_features(x)
+        return None, ops.linear(feats, self.w["cls_w"], self.w["cls_b"])
+
+    __call__ = forward
+
+
+class TokenWrapper(_Extractor):
+    """models/token_based.py:162-189: training-loop facade over TokenModel."""
+
+    in_channels = 4
+
+    def __init__(self, num_classes, backbone="resnet50", feature_dim=2048, hidden_dim=512, num_heads=8, num_layers=2,
+                 **kw):
+        self.backbone = TokenModel(backbone=backbone, num_classes=num_classes, feature_dim=feature_dim,
+                                   hidden_dim=hidden_dim, num_heads=num_heads, num_layers=num_layers, **kw)
+        self.outputdim = self.backbone.outputdim
+
+    def forward_test_nhwc(self, x_nhwc, hook=None):
+        return self.backbone.forward_test_nhwc(x_nhwc, hook)
+
+    @torch.no_grad()
+    def forward(self, x, targets=None):
+        return self.backbone(x)
+
+    __call__ = forward
+
+    def extract_features(self, x):
+        return self.backbone.extract_features(x)
+
+    def extract_descriptor(self, x):
+        return self.backbone.extract_descriptor(x)
+
+    def extract_global_descriptor(self, x):
+        return self.backbone.extract_descriptor(x)
+
+
+def get_token_model(num_classes, backbone="resnet50", **kwargs):
+    return TokenWrapper(num_classes=num_classes, backbone=backbone, **kwargs)
 
 
 MODEL_REGISTRY = {

@@ -633,10 +633,11 @@ def sos_cov(z, hid, w3, b3, want_att=False):
     return (out, inv, att) if want_att else (out, inv)
 
 
-def linear_splitk(x, w, bias, row_scale=None, act=0):
-    """y = act(row_scale[:, None] * (x @ w.T) + bias) on the split-K path
-    (rr_linear_splitk): x [M,K], w [N,K], K % 4 == 0; bias [N] and row_scale [M]
-    may be None; act 0 none, 1 ReLU, 2 QuickGELU."""
+def linear_splitk(x, w, bias, row_scale=None, act=0, residual=None):
+    """y = act(row_scale[:, None] * (x @ w.T) + bias + residual) on the split-K
+    path (rr_linear_splitk; with a residual [M,N] rr_linear_splitk_ex): x [M,K],
+    w [N,K], K % 4 == 0; bias [N], row_scale [M] and residual may be None; act 0
+    none, 1 ReLU, 2 QuickGELU."""
     _f32(x, "linear_splitk x")
     _f32(w, "linear_splitk w")
     if x.dim() != 2 or w.dim() != 2 or w.shape[1] != x.shape[1]:
@@ -650,6 +651,9 @@ def linear_splitk(x, w, bias, row_scale=None, act=0):
     if row_scale is not None and (_f32(row_scale, "linear_splitk row_scale").numel() != m or
                                   row_scale.device != x.device):
         raise ValueError(f"linear_splitk: row_scale must be [{m}] on x's device")
+    if residual is not None and (tuple(_f32(residual, "linear_splitk residual").shape) != (m, n) or
+                                 residual.device != x.device):
+        raise ValueError(f"linear_splitk: residual must be [{m},{n}] on x's device")
     if int(act) not in (0, 1, 2):
         raise ValueError("linear_splitk: act must be 0, 1 or 2")
     dev = _dev(x)
@@ -659,9 +663,39 @@ def linear_splitk(x, w, bias, row_scale=None, act=0):
     if m == 0:
         return y
     hd = _lib.handle(dev)
-    _lib.check(_lib.lib().rr_linear_splitk(hd, _ptr(x), m, k, _ptr(w), n, _ptr(row_scale), _ptr(bias), int(act),
-                                           _ptr(y), _stream(dev)), hd, "rr_linear_splitk")
+    if residual is None:
+        _lib.check(_lib.lib().rr_linear_splitk(hd, _ptr(x), m, k, _ptr(w), n, _ptr(row_scale), _ptr(bias), int(act),
+                                               _ptr(y), _stream(dev)), hd, "rr_linear_splitk")
+    else:
+        _lib.check(_lib.lib().rr_linear_splitk_ex(hd, _ptr(x), m, k, _ptr(w), n, _ptr(row_scale), _ptr(bias),
+                                                  _ptr(residual), int(act), _ptr(y), _stream(dev)), hd,
+                   "rr_linear_splitk_ex")
     return y
+
+
+def cls_attn_pool(x, qt, want_p=False):
+    """The token aggregator's folded last-layer attention (rr_cls_attn_pool):
+    x [B,seq,D] the layer's input rows, qt [B,heads,D] the folded scaled
+    queries -> out [B,heads,D] = sum_j softmax_j(qt_h . x_j) x_j, and p
+    [B,heads,seq] as a second value with want_p."""
+    _f32(x, "cls_attn_pool x")
+    _f32(qt, "cls_attn_pool qt")
+    if x.dim() != 3 or qt.dim() != 3 or qt.shape[0] != x.shape[0] or qt.shape[2] != x.shape[2]:
+        raise ValueError(f"cls_attn_pool: x [B,seq,D] and qt [B,heads,D], got {tuple(x.shape)} and {tuple(qt.shape)}")
+    b, seq, d = x.shape
+    heads = qt.shape[1]
+    if d % 64 or not 64 <= d <= 1024 or not 1 <= heads <= 16 or not 1 <= seq <= 256:
+        raise ValueError("cls_attn_pool: d % 64 == 0, 64 <= d <= 1024, 1 <= heads <= 16, 1 <= seq <= 256")
+    dev = _dev(x)
+    if qt.device != x.device:
+        raise ValueError("cls_attn_pool: x and qt must be on one device")
+    out = torch.empty((b, heads, d), dtype=torch.float32, device=x.device)
+    p = torch.empty((b, heads, seq), dtype=torch.float32, device=x.device) if want_p else None
+    if b:
+        hd = _lib.handle(dev)
+        _lib.check(_lib.lib().rr_cls_attn_pool(hd, _ptr(x), b, seq, d, _ptr(qt), heads, _ptr(p), _ptr(out),
+                                               _stream(dev)), hd, "rr_cls_attn_pool")
+    return (out, p) if want_p else out
 
 
 def gelu(x, out=None):

@@ -9,6 +9,7 @@ versions) so the oracle, the tests and bench.py all rebuild identical weights
 from a seed.
 """
 import collections
+import math
 
 import numpy as np
 import torch
@@ -496,6 +497,195 @@ def synthetic_sos_head(seed, second_order_dim=512, num_classes=8, use_attention=
     lin("second_order_pool.proj", c, 2048, shape=(c, 2048, 1, 1))
     lin("feature_proj.0", feature_dim, c * (c + 1) // 2)
     lin("feature_proj.3", feature_dim, feature_dim)
+    lin("classifier", num_classes, feature_dim)
+    return sd
+
+
+# ---- token aggregator head (models/token_based.py:13-159) -------------------
+# (networks.Token / token_head_from_state_dict below are the OTHER token model,
+# networks/RetrievalNet.py's Token_Refine.)
+_TA = "token_aggregator."
+TOKAGG_LAYER_KEYS = ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight",
+                     "self_attn.out_proj.bias", "linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias",
+                     "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias")
+_TOKAGG_LAYER_NAMES = ("qkv_w", "qkv_b", "out_w", "out_b", "l1_w", "l1_b", "l2_w", "l2_b", "n1_g", "n1_b", "n2_g",
+                       "n2_b")
+TOKAGG_PE_KEY = _TA + "pos_encoding.pe"  # optional: a buffer, recomputed when absent
+TOKAGG_MAX_LEN = 196  # PositionalEncoding's max_len (:16): the model takes no more positions
+
+
+def tokagg_head_keys(num_layers=2):
+    keys = [_TA + "input_proj.weight", _TA + "input_proj.bias", _TA + "global_token"]
+    keys += [f"{_TA}transformer.layers.{i}.{k}" for i in range(num_layers) for k in TOKAGG_LAYER_KEYS]
+    return tuple(keys) + (_TA + "output_proj.weight", _TA + "output_proj.bias", "feature_proj.weight",
+                          "feature_proj.bias", "classifier.weight", "classifier.bias")
+
+
+TOKAGG_QK_GAIN = 3.5  # synthetic_tokagg_head: the gain of in_proj's q and k rows over PyTorch's default init
+
+
+def tokagg_positional_encoding(d_model, max_len=TOKAGG_MAX_LEN):
+    """PositionalEncoding's buffer (:19-25) as [max_len, d_model], in float32
+    with the reference's own expression (the same bits as its registered pe)."""
+    pe = torch.zeros(max_len, d_model)
+    position = torch.arange(0, max_len, dtype=torch.float).unsqueeze(1)
+    div_term = torch.exp(torch.arange(0, d_model, 2).float() * (-math.log(10000.0) / d_model))
+    pe[:, 0::2] = torch.sin(position * div_term)
+    pe[:, 1::2] = torch.cos(position * div_term)
+    return pe
+
+
+def tokagg_head_from_state_dict(sd):
+    """The token aggregator's head of a reference checkpoint (TokenModel's keys
+    token_aggregator.{input_proj.*, pos_encoding.pe, global_token,
+    transformer.layers.{i}.*, output_proj.*}, feature_proj.*, classifier.*, bare
+    or under the wrapper's leading ``backbone.``, a ``module.`` before either
+    dropped; trunk keys are ignored) as fp32 contiguous tensors:
+
+      in_w [d,Cin], in_b, pe [max_len,d] (computed when the buffer is absent),
+      global_token [d], per layer i: l{i}_qkv_w [3d,d] (q | k | v), l{i}_qkv_b,
+      l{i}_out_w [d,d], l{i}_out_b, l{i}_l1_w [f,d], l{i}_l1_b, l{i}_l2_w [d,f],
+      l{i}_l2_b, l{i}_n1_g, l{i}_n1_b, l{i}_n2_g, l{i}_n2_b; op_w [Cin,d], op_b,
+      fp_w [F,Cin], fp_b, cls_w [classes,F], cls_b.
+
+    The layer count is the number of consecutive transformer.layers.{i} found."""
+    flat = {}
+    for k, v in sd.items():
+        for lead in ("module.", "backbone."):
+            if k.startswith(lead):
+                k = k[len(lead):]
+        flat.setdefault(k, v)
+    layers = 0
+    while any(f"{_TA}transformer.layers.{layers}.{k}" in flat for k in TOKAGG_LAYER_KEYS):
+        layers += 1
+    missing = [k for k in tokagg_head_keys(max(layers, 1)) if k not in flat]
+    if missing:
+        raise ValueError(f"token aggregator head: missing keys {missing}")
+    f = lambda a: a.float().contiguous()  # noqa: E731
+    in_w, gt = flat[_TA + "input_proj.weight"], flat[_TA + "global_token"]
+    if in_w.dim() != 2:
+        raise ValueError(f"token_aggregator.input_proj.weight: expected [d,Cin], got {tuple(in_w.shape)}")
+    d, cin = in_w.shape
+    if gt.numel() != d:
+        raise ValueError(f"token_aggregator.global_token: expected {d} values, got {tuple(gt.shape)}")
+    head = {"in_w": f(in_w), "in_b": f(flat[_TA + "input_proj.bias"]), "global_token": f(gt.reshape(d))}
+    if TOKAGG_PE_KEY in flat:
+        pe = flat[TOKAGG_PE_KEY]
+        if pe.dim() != 3 or pe.shape[1] != 1 or pe.shape[2] != d:
+            raise ValueError(f"token_aggregator.pos_encoding.pe: expected [max_len,1,{d}], got {tuple(pe.shape)}")
+        head["pe"] = f(pe.reshape(pe.shape[0], d))
+    else:
+        head["pe"] = tokagg_positional_encoding(d)
+    for i in range(layers):
+        pre = f"{_TA}transformer.layers.{i}."
+        shapes = {"qkv_w": (3 * d, d), "qkv_b": (3 * d,), "out_w": (d, d), "out_b": (d,), "l1_b": None, "l2_b": (d,),
+                  "n1_g": (d,), "n1_b": (d,), "n2_g": (d,), "n2_b": (d,)}
+        ffn = flat[pre + "linear1.weight"].shape[0]
+        shapes.update(l1_w=(ffn, d), l1_b=(ffn,), l2_w=(d, ffn))
+        for key, name in zip(TOKAGG_LAYER_KEYS, _TOKAGG_LAYER_NAMES):
+            t = flat[pre + key]
+            if tuple(t.shape) != shapes[name]:
+                raise ValueError(f"{pre + key}: expected {list(shapes[name])}, got {tuple(t.shape)}")
+            head[f"l{i}_{name}"] = f(t)
+    ow, fw, cw = flat[_TA + "output_proj.weight"], flat["feature_proj.weight"], flat["classifier.weight"]
+    if ow.dim() != 2 or ow.shape[1] != d or ow.shape[0] != cin:
+        raise ValueError(f"token_aggregator.output_proj.weight: expected [{cin},{d}], got {tuple(ow.shape)}")
+    if fw.dim() != 2 or fw.shape[1] != cin:
+        raise ValueError(f"feature_proj.weight: expected [F,{cin}], got {tuple(fw.shape)}")
+    if cw.dim() != 2 or cw.shape[1] != fw.shape[0]:
+        raise ValueError(f"classifier.weight: expected [classes,{fw.shape[0]}], got {tuple(cw.shape)}")
+    head.update(op_w=f(ow), op_b=f(flat[_TA + "output_proj.bias"]), fp_w=f(fw), fp_b=f(flat["feature_proj.bias"]),
+                cls_w=f(cw), cls_b=f(flat["classifier.bias"]))
+    return head
+
+
+def tokagg_num_layers(head):
+    n = 0
+    while f"l{n}_qkv_w" in head:
+        n += 1
+    return n
+
+
+def tokagg_layer(head, i):
+    """Layer i of a tokagg_head_from_state_dict head, keyed without the l{i}_ lead."""
+    return {name: head[f"l{i}_{name}"] for name in _TOKAGG_LAYER_NAMES}
+
+
+def tokagg_fold_last_layer(layer, heads, dtype=torch.float32):
+    """The last encoder layer's attention folded for the global token alone
+    ("The token aggregator"): layer holds qkv_w [3d,d], qkv_b, out_w
+    [d,d], out_b; with e = d / heads and W_h the head's e rows,
+
+      A  = [Wk_h^T Wq_h / sqrt(e)]_h   [heads d, d]    a0 = [Wk_h^T bq_h / sqrt(e)]_h
+      M  = [Wo[:, h] Wv_h]_h           [d, heads d]    m0 = Wo bv + bo
+
+    so q~ = A x0 + a0, p_h = softmax_j(q~_h . x_j), and the attention block's
+    output is M [sum_j p_hj x_j]_h + m0.  The key bias is never read (it shifts
+    a head's scores alike).  Products in float64 on the host, stored as fp32
+    (dtype: tests ask for the float64 products)."""
+    w, b = layer["qkv_w"].double(), layer["qkv_b"].double()
+    wo, bo = layer["out_w"].double(), layer["out_b"].double()
+    d = w.shape[1]
+    if d % heads:
+        raise ValueError(f"tokagg_fold_last_layer: {heads} heads do not divide width {d}")
+    e = d // heads
+    wq, wk, wv = w[:d].view(heads, e, d), w[d:2 * d].view(heads, e, d), w[2 * d:].view(heads, e, d)
+    bq, bv = b[:d].view(heads, e), b[2 * d:]
+    s = 1.0 / math.sqrt(e)
+    a = torch.bmm(wk.transpose(1, 2), wq) * s                      # [heads, d, d]
+    a0 = torch.bmm(wk.transpose(1, 2), bq.unsqueeze(2)).squeeze(2) * s
+    m = torch.bmm(wo.view(d, heads, e).permute(1, 0, 2), wv)       # [heads, d, d]: Wo[:, h] Wv_h
+    m0 = wo @ bv + bo
+    f = lambda t: t.to(dtype).contiguous()  # noqa: E731
+    return f(a.reshape(heads * d, d)), f(a0.reshape(heads * d)), f(m.permute(1, 0, 2).reshape(d, heads * d)), f(m0)
+
+
+def synthetic_tokagg_head(seed, hidden_dim=512, num_heads=8, num_layers=2, num_classes=8, feature_dim=2048,
+                          in_dim=2048, qk_gain=TOKAGG_QK_GAIN):
+    """Seeded token-aggregator weights under TokenModel's keys
+    (tokagg_head_keys), drawn as PyTorch's default initialisers draw them:
+    every Linear U(+-1 / sqrt(fan_in)) for weight and bias, in_proj_weight
+    Xavier-uniform U(+-sqrt(6 / (4 d))), global_token N(0, 1).  Three
+    departures, so that a wrong head cannot pass:
+     - the q and k rows of in_proj_weight are drawn qk_gain = 3.5 times wider
+       (scores grow with its square):
+       with the default init the global token's attention is near-uniform
+       (max_j p a few times 1 / N) and a head that averaged the rows would pass;
+       with the gain most (image, head) pairs have 0.2 <= max_j p <= 0.99
+       (asserted by tests/golden/make_golden_tokagg.py);
+     - in_proj_bias and out_proj.bias, zero by default, are U(+-1 / sqrt(d)), so
+       the folded biases a0 and m0 are exercised;
+     - LayerNorm weights are 1 + 0.1 u and biases 0.1 u, u ~ U(-1, 1).
+    num_heads only checks the width; the draw does not depend on it.  The pe
+    buffer is not included (the loader computes it)."""
+    if hidden_dim % num_heads:
+        raise ValueError("synthetic_tokagg_head: num_heads must divide hidden_dim")
+    rs = np.random.RandomState(seed)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
+    sd = collections.OrderedDict()
+    d = hidden_dim
+
+    def lin(key, out_dim, in_d):
+        s = 1.0 / np.sqrt(in_d)
+        sd[key + ".weight"] = t(rs.uniform(-1, 1, (out_dim, in_d)) * s)
+        sd[key + ".bias"] = t(rs.uniform(-1, 1, out_dim) * s)
+
+    lin(_TA + "input_proj", d, in_dim)
+    sd[_TA + "global_token"] = t(rs.standard_normal((1, 1, d)))
+    for i in range(num_layers):
+        pre = f"{_TA}transformer.layers.{i}."
+        w = rs.uniform(-1, 1, (3 * d, d)) * np.sqrt(6.0 / (4 * d))
+        w[:2 * d] *= qk_gain
+        sd[pre + "self_attn.in_proj_weight"] = t(w)
+        sd[pre + "self_attn.in_proj_bias"] = t(rs.uniform(-1, 1, 3 * d) / np.sqrt(d))
+        lin(pre + "self_attn.out_proj", d, d)
+        lin(pre + "linear1", 4 * d, d)
+        lin(pre + "linear2", d, 4 * d)
+        for n in ("norm1", "norm2"):
+            sd[pre + n + ".weight"] = t(1 + 0.1 * rs.uniform(-1, 1, d))
+            sd[pre + n + ".bias"] = t(0.1 * rs.uniform(-1, 1, d))
+    lin(_TA + "output_proj", in_dim, d)
+    lin("feature_proj", feature_dim, in_dim)
     lin("classifier", num_classes, feature_dim)
     return sd
 

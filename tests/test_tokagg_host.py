@@ -1,0 +1,331 @@
+"""The token aggregator without a GPU: the new C-ABI entry, the head-weight
+loader, the fold of the last layer, the constructor's checks, and the torch
+restatement (tests/tokagg_ref.py) pinned to the reference's own TokenModel /
+TokenAggregator output (tests/golden/tokagg.npz, make_golden_tokagg.py)."""
+import collections
+import ctypes
+import hashlib
+import inspect
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from research_image_retrieval_amd import _lib, models, ops
+from research_image_retrieval_amd import weights as W
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLD = os.path.join(HERE, "golden")
+sys.path.insert(0, GOLD)
+sys.path.insert(0, HERE)
+import inputs as I  # noqa: E402
+import tokagg_ref  # noqa: E402
+
+TAGS = ("b2_224", "b1_odd")
+HEAD_CASES = ((2, 7, 7), (1, 5, 9), (1, 14, 14), (1, 1, 1))
+HEADS = 8
+BAR = 1e-6
+# each degenerate replacement of a piece of the head (tokagg_ref.head_forward's switches)
+SWITCHES = ({"uniform_last": True}, {"positional": False}, {"global_token": False}, {"skip_layer0": True})
+
+
+def _tag(b, h, w):
+    return f"head_b{b}_{h}x{w}"
+
+
+def _head_input(b, h, w):
+    return torch.from_numpy(I.feature_map(13000 + h * w, b, 2048, h, w))
+
+
+def _row_err(got, ref):
+    got, ref = torch.as_tensor(got).double(), torch.as_tensor(ref).double()
+    return ((got - ref).abs().amax(dim=-1) / ref.norm(dim=-1)).max().item()
+
+
+@pytest.fixture(scope="module")
+def fx():
+    return np.load(os.path.join(GOLD, "tokagg.npz"))
+
+
+@pytest.fixture(scope="module")
+def head(fx):
+    return W.tokagg_head_from_state_dict(W.synthetic_tokagg_head(int(fx["head_seed"]), 512, HEADS, 2, 8, 2048))
+
+
+@pytest.fixture(scope="module")
+def refs(head):
+    """The float64 and float32 literal restatements of every group-(b) case, computed once."""
+    return {c: {dt: tokagg_ref.head_forward(_head_input(*c), head, HEADS, dt) for dt in (torch.float64, torch.float32)}
+            for c in HEAD_CASES}
+
+
+def test_symbol_and_abi():
+    L = ctypes.CDLL(_lib.LIB_PATH)
+    assert hasattr(L, "rr_cls_attn_pool") and "rr_cls_attn_pool" in _lib.SIGNATURES
+    assert len(_lib.SIGNATURES["rr_cls_attn_pool"][1]) == 10
+    L = _lib.lib()
+    assert L.rr_abi_version() == 7 == _lib.ABI_VERSION
+    assert L.rr_cls_attn_pool(None, None, 1, 2, 64, None, 1, None, None, None) == _lib.RR_EINVAL
+    assert "rr_linear_splitk_ex" in _lib.SIGNATURES and len(_lib.SIGNATURES["rr_linear_splitk_ex"][1]) == 12
+    assert L.rr_linear_splitk_ex(None, None, 1, 4, None, 1, None, None, None, 0, None, None) == _lib.RR_EINVAL
+
+
+def test_fixture_is_within_the_other_fixtures_sizes(fx):
+    size = os.path.getsize(os.path.join(GOLD, "tokagg.npz"))
+    assert size < os.path.getsize(os.path.join(GOLD, "token.npz")) and size < os.path.getsize(os.path.join(GOLD, "how.npz"))
+    assert not [k for k in fx.files if k.endswith("_x4") or k.endswith("_input")]  # inputs come from seeds
+
+
+@pytest.mark.parametrize("case", HEAD_CASES)
+def test_restatement_reproduces_head_fixture(fx, refs, case):
+    """Every stored array of the head group against the literal restatement in
+    float32 and in float64: max(1e-6, 4 x the float32-vs-float64 restatement
+    error) of the row norm, the bar of the other heads' tests.  The stored
+    arrays are float32 outputs of the reference, so the float64 restatement
+    sits at the reference's own float32 noise.  All are printed.  With more
+    than two rows, the attention conditions of make_golden_tokagg.py hold."""
+    tag = _tag(*case)
+    r32, r64 = refs[case][torch.float32], refs[case][torch.float64]
+    stored = ["out"] + (["agg", "features"] if case == (1, 5, 9) else [])
+    pm = r64["p"].amax(dim=-1).reshape(-1)
+    print(tag, "max_j p in", float(pm.min()), float(pm.max()))
+    if 1 + case[1] * case[2] > 2:
+        assert float((pm >= 0.2).double().mean()) >= 0.5 and float((pm <= 0.99).double().mean()) >= 0.5
+    for key in stored:
+        ref = fx[f"{tag}_{key}"]
+        assert ref.shape == tuple(r32[key].shape), key
+        e32, e64, d = _row_err(r32[key], ref), _row_err(r64[key], ref), _row_err(r32[key], r64[key])
+        print(f"  {tag} {key}: float32 restatement vs reference {e32:.3e}, float64 {e64:.3e} of the row norm; float32 vs "
+              f"float64 restatement {d:.3e}")
+        assert e32 <= max(BAR, 4 * d) and e64 <= max(BAR, 4 * d), key
+    assert fx[tag + "_out"].shape == (case[0], 2048)
+
+
+def test_layer0_reproduces_the_reference_layer(fx, head, refs):
+    """The reference's own transformer.layers[0], called directly on the tokens
+    of (1, 5, 9), against encoder_layer on the restatement's tokens."""
+    case = (1, 5, 9)
+    ref = torch.from_numpy(fx[_tag(*case) + "_layer0"])
+    assert ref.shape == (1, 46, 512)
+    layer = W.tokagg_layer(head, 0)
+    got = {dt: tokagg_ref.encoder_layer(refs[case][dt]["tokens"], layer, HEADS, dt) for dt in (torch.float32, torch.float64)}
+    e32, e64 = _row_err(got[torch.float32], ref), _row_err(got[torch.float64], ref)
+    d = _row_err(got[torch.float32], got[torch.float64])
+    print(f"layers[0] on 46 tokens: float32 {e32:.3e}, float64 {e64:.3e}; float32 vs float64 restatement {d:.3e}")
+    assert e32 <= max(BAR, 4 * d) and e64 <= max(BAR, 4 * d)
+    assert _row_err(got[torch.float64], refs[case][torch.float64]["layer_out"]) == 0.0  # the last layer's input
+
+
+@pytest.mark.parametrize("tag", TAGS)
+def test_restatement_reproduces_end_to_end_fixture(fx, head, tag):
+    """Group (a), from the reference trunk's saved x4 (wiring)."""
+    tr = np.load(os.path.join(GOLD, "resnet_dolg_v15.npz"))
+    assert int(tr["weight_seed"]) == int(fx["weight_seed"])
+    assert list(tr[tag + "_case"]) == list(fx[tag + "_case"])
+    x4 = torch.from_numpy(tr[tag + "_x4"])
+    r32 = tokagg_ref.head_forward(x4, head, HEADS, torch.float32)
+    r64 = tokagg_ref.head_forward(x4, head, HEADS, torch.float64)
+    e, e64, d = _row_err(r32["out"], fx[tag + "_out"]), _row_err(r64["out"], fx[tag + "_out"]), \
+        _row_err(r32["out"], r64["out"])
+    print(tag, "descriptor: float32 vs reference", e, "; float64", e64, "; float32 vs float64 restatement", d)
+    assert e <= max(BAR, 4 * d) and e64 <= max(BAR, 4 * d)
+
+
+@pytest.mark.parametrize("case", HEAD_CASES)
+def test_folded_last_layer_equals_the_literal_one(head, refs, case):
+    """The fold (weights.tokagg_fold_last_layer) around the pooling the kernel
+    computes, against row 0 of the literal layer over all rows: <= 1e-12 of the
+    row norm in float64, and in float32 (fp32-stored A, a0, M, m0) as close to
+    float64 as the literal float32 layer, times 4."""
+    r64, r32 = refs[case][torch.float64], refs[case][torch.float32]
+    layer = W.tokagg_layer(head, 1)
+    lit64 = tokagg_ref.encoder_layer(r64["layer_out"], layer, HEADS, torch.float64)[:, 0]
+    lit32 = tokagg_ref.encoder_layer(r64["layer_out"].float(), layer, HEADS, torch.float32)[:, 0]
+    taps = {}
+    f64 = tokagg_ref.last_layer_folded(r64["layer_out"], layer, HEADS, torch.float64, taps)
+    f32 = tokagg_ref.last_layer_folded(r64["layer_out"].float(), layer, HEADS, torch.float32)
+    e64, e32, d32 = _row_err(f64, lit64), _row_err(f32, lit64), _row_err(lit32, lit64)
+    print(f"{_tag(*case)}: folded float64 {e64:.3e}, folded float32 {e32:.3e}, literal float32 {d32:.3e} of the row norm")
+    assert e64 <= 1e-12
+    assert e32 <= max(BAR, 4 * d32)
+    assert _row_err(taps["p"], r64["p"]) <= 1e-12 and _row_err(taps["pooled"], r64["pooled"]) <= 1e-12
+    a, a0, m, m0 = W.tokagg_fold_last_layer(layer, HEADS)
+    assert a.shape == (HEADS * 512, 512) and a0.shape == (HEADS * 512,) and m.shape == (512, HEADS * 512)
+    assert m0.shape == (512,) and all(t.dtype == torch.float32 and t.is_contiguous() for t in (a, a0, m, m0))
+    assert a.numel() * 4 == m.numel() * 4 == 8 * 2 ** 20  # 8 MB each at the defaults
+
+
+def test_fold_never_reads_the_key_bias(head):
+    layer = dict(W.tokagg_layer(head, 1))
+    ref = W.tokagg_fold_last_layer(layer, HEADS)
+    layer["qkv_b"] = layer["qkv_b"].clone()
+    layer["qkv_b"][512:1024] += 7.0
+    assert all(torch.equal(x, y) for x, y in zip(ref, W.tokagg_fold_last_layer(layer, HEADS)))
+    with pytest.raises(ValueError, match="heads"):
+        W.tokagg_fold_last_layer(layer, 7)
+
+
+def test_computed_pe_is_the_reference_buffer(fx):
+    """weights.tokagg_positional_encoding against the reference's registered
+    buffer: the SHA-256 of all 196 x 512 floats and eight stored rows, bit for
+    bit; a state dict that carries the buffer round-trips it."""
+    pe = W.tokagg_positional_encoding(512)
+    assert pe.shape == (196, 512) and pe.dtype == torch.float32
+    assert hashlib.sha256(pe.numpy().tobytes()).digest() == fx["pe_sha256"].tobytes()
+    rows = [int(r) for r in fx["pe_rows"]]
+    assert np.array_equal(pe[rows].numpy().view(np.int32), fx["pe_values"].view(np.int32))
+    sd = W.synthetic_tokagg_head(3, 64, 1, 1)
+    assert W.TOKAGG_PE_KEY not in sd
+    h = W.tokagg_head_from_state_dict(sd)
+    assert torch.equal(h["pe"], W.tokagg_positional_encoding(64))
+    stored = torch.arange(196 * 64, dtype=torch.float32).reshape(196, 1, 64)
+    sd["backbone." + W.TOKAGG_PE_KEY] = stored
+    assert torch.equal(W.tokagg_head_from_state_dict(sd)["pe"], stored.reshape(196, 64))
+
+
+@pytest.mark.parametrize("case", HEAD_CASES)
+def test_head_fixture_is_sensitive_to_every_piece(head, refs, case):
+    """A condition on the fixture: each degenerate replacement (a uniform
+    softmax in the last layer, no positional term, a zero global token, layer 0
+    skipped) moves the float64 descriptor by at least 100 x the bar the GPU
+    descriptor is held to on this case, max(2e-6, 4 x float32-vs-float64)."""
+    r64, r32 = refs[case][torch.float64], refs[case][torch.float32]
+    bar = max(2e-6, 4 * (r32["out"].double() - r64["out"]).abs().max().item())
+    x = _head_input(*case)
+    for sw in SWITCHES:
+        moved = (tokagg_ref.head_forward(x, head, HEADS, torch.float64, **sw)["out"] - r64["out"]).abs().max().item()
+        print(_tag(*case), sw, "moves the descriptor by", moved, "=", moved / bar, "x the bar", bar)
+        assert moved >= 100 * bar, sw
+
+
+def _checkpoint(seed, lead, with_pe):
+    """A reference-shaped checkpoint: index-named nn.Sequential trunk keys
+    under `lead`backbone., head keys under `lead`."""
+    tv = W.synthetic_resnet_state_dict("resnet50", seed)
+    inv = {v: k for k, v in {"0": "conv1", "1": "bn1", "4": "layer1", "5": "layer2", "6": "layer3",
+                             "7": "layer4"}.items()}
+    sd = collections.OrderedDict()
+    for k, v in tv.items():
+        first, rest = k.split(".", 1)
+        sd[f"{lead}backbone.{inv[first]}.{rest}"] = v
+    for k, v in W.synthetic_tokagg_head(seed + 1, 128, 2, 3, 8, 256).items():
+        sd[lead + k] = v
+    if with_pe:
+        sd[lead + W.TOKAGG_PE_KEY] = W.tokagg_positional_encoding(128).unsqueeze(1)
+    return sd, tv
+
+
+@pytest.mark.parametrize("with_pe", [True, False])
+@pytest.mark.parametrize("lead", ["", "backbone.", "module.backbone."])
+def test_head_from_state_dict_round_trips(lead, with_pe):
+    sd, tv = _checkpoint(5, lead, with_pe)
+    raw = W.synthetic_tokagg_head(6, 128, 2, 3, 8, 256)
+    h = W.tokagg_head_from_state_dict(sd)
+    assert all(v.dtype == torch.float32 and v.is_contiguous() for v in h.values())
+    assert W.tokagg_num_layers(h) == 3
+    ta = "token_aggregator."
+    assert h["in_w"].shape == (128, 2048) and torch.equal(h["in_w"], raw[ta + "input_proj.weight"])
+    assert h["global_token"].shape == (128,) and torch.equal(h["global_token"], raw[ta + "global_token"].reshape(128))
+    assert h["pe"].shape == (196, 128) and torch.equal(h["pe"], W.tokagg_positional_encoding(128))
+    for i in range(3):
+        pre = f"{ta}transformer.layers.{i}."
+        lay = W.tokagg_layer(h, i)
+        assert lay["qkv_w"].shape == (384, 128) and torch.equal(lay["qkv_w"], raw[pre + "self_attn.in_proj_weight"])
+        assert torch.equal(lay["qkv_b"], raw[pre + "self_attn.in_proj_bias"])
+        assert torch.equal(lay["out_w"], raw[pre + "self_attn.out_proj.weight"])
+        assert lay["l1_w"].shape == (512, 128) and torch.equal(lay["l2_w"], raw[pre + "linear2.weight"])
+        assert torch.equal(lay["n1_g"], raw[pre + "norm1.weight"]) and torch.equal(lay["n2_b"], raw[pre + "norm2.bias"])
+    assert h["op_w"].shape == (2048, 128) and torch.equal(h["op_b"], raw[ta + "output_proj.bias"])
+    assert h["fp_w"].shape == (256, 2048) and torch.equal(h["fp_w"], raw["feature_proj.weight"])
+    assert h["cls_w"].shape == (8, 256) and torch.equal(h["cls_b"], raw["classifier.bias"])
+    # the documented departures from PyTorch's default init
+    w = raw[ta + "transformer.layers.0.self_attn.in_proj_weight"]
+    assert float(w[:256].abs().max()) > 3.0 * float(w[256:].abs().max())
+    assert float(raw[ta + "transformer.layers.0.self_attn.in_proj_bias"].abs().max()) > 0
+    back = W.to_torchvision_keys(sd)
+    assert set(back) == set(tv) and all(torch.equal(back[k], tv[k]) for k in tv)
+
+
+def test_head_rejects_missing_keys_and_bad_shapes():
+    sd = W.synthetic_tokagg_head(7, 64, 1, 2, 8, 128)
+    for k in W.tokagg_head_keys(2):
+        bad = dict(sd)
+        bad.pop(k)
+        with pytest.raises(ValueError, match=k.replace(".", r"\.")):
+            W.tokagg_head_from_state_dict(bad)
+    with pytest.raises(ValueError, match="missing"):
+        W.tokagg_head_from_state_dict({})
+    ta = "token_aggregator."
+    for k, shape in ((ta + "global_token", (1, 1, 32)), (ta + "transformer.layers.1.self_attn.in_proj_weight", (128, 64)),
+                     (ta + "transformer.layers.0.linear2.weight", (64, 100)), (ta + "output_proj.weight", (2048, 32)),
+                     ("feature_proj.weight", (128, 512)), ("classifier.weight", (8, 64)),
+                     (ta + "pos_encoding.pe", (196, 64))):
+        bad = dict(sd)
+        bad[k] = torch.zeros(shape)
+        with pytest.raises(ValueError, match=k.split(".")[0]):
+            W.tokagg_head_from_state_dict(bad)
+
+
+def test_constructor_order_and_argument_errors():
+    names = list(inspect.signature(models.TokenModel.__init__).parameters)[1:]
+    assert names == ["backbone", "pretrained", "num_classes", "feature_dim", "hidden_dim", "num_heads", "num_layers",
+                     "state_dict", "seed", "device", "conv_math", "stride_on"]
+    assert list(inspect.signature(models.TokenWrapper.__init__).parameters)[1:7] == [
+        "num_classes", "backbone", "feature_dim", "hidden_dim", "num_heads", "num_layers"]
+    p = inspect.signature(models.TokenModel.__init__).parameters
+    assert (p["hidden_dim"].default, p["num_heads"].default, p["num_layers"].default) == (512, 8, 2)
+    # argument errors come before any device work (this container has no device)
+    with pytest.raises(ValueError, match="pretrained"):
+        models.TokenModel(pretrained=True)
+    with pytest.raises(ValueError, match="backbone"):
+        models.get_token_model(10, backbone="resnet18")
+    for d in (0, 32, 96, 1088, 2048):
+        with pytest.raises(ValueError, match="hidden_dim"):
+            models.get_token_model(10, hidden_dim=d, num_heads=1, num_layers=1)
+    for nh in (0, 17, 3, 32):
+        with pytest.raises(ValueError, match="num_heads"):
+            models.get_token_model(10, hidden_dim=512, num_heads=nh, num_layers=1)
+    with pytest.raises(ValueError, match="64 num_heads"):
+        models.get_token_model(10, hidden_dim=512, num_heads=4, num_layers=2)
+    with pytest.raises(ValueError, match="num_layers"):
+        models.get_token_model(10, num_layers=0)
+    with pytest.raises(ValueError, match="shapes"):
+        models.TokenModel(num_layers=3, state_dict=W.synthetic_tokagg_head(3, 512, 8, 2))
+
+
+def test_more_than_196_positions_raise():
+    """The model's check comes before any launch, so it runs without a device;
+    the restatement raises as the reference's broadcast does."""
+    m = models.TokenModel.__new__(models.TokenModel)
+    m.max_len, m.hidden_dim = 196, 512
+    with pytest.raises(ValueError, match="max_len = 196"):
+        m.head(torch.zeros(1, 14, 15, 2048))
+    head = W.tokagg_head_from_state_dict(W.synthetic_tokagg_head(3, 64, 1, 1, 8, 64, in_dim=64))
+    with pytest.raises(ValueError, match="max_len"):
+        tokagg_ref.tokens(torch.zeros(1, 64, 14, 15), head)
+    assert tokagg_ref.tokens(torch.zeros(1, 64, 14, 14), head).shape == (1, 197, 64)
+
+
+def test_ops_reject_bad_shapes_before_the_call():
+    z = torch.zeros
+    for x, qt in ((z(1, 4, 96), z(1, 1, 96)), (z(1, 4, 32), z(1, 1, 32)), (z(1, 4, 1088), z(1, 1, 1088)),
+                  (z(1, 257, 64), z(1, 1, 64)), (z(1, 0, 64), z(1, 1, 64)), (z(1, 4, 64), z(1, 17, 64)),
+                  (z(1, 4, 64), z(1, 0, 64)), (z(1, 4, 64), z(2, 1, 64)), (z(1, 4, 64), z(1, 1, 128)),
+                  (z(4, 64), z(1, 64)), (z(1, 4, 128)[:, :, ::2], z(1, 1, 64)), (z(1, 4, 64).double(), z(1, 1, 64))):
+        with pytest.raises((ValueError, TypeError)):
+            ops.cls_attn_pool(x, qt)
+    with pytest.raises(ValueError, match="ROCm"):   # a good shape reaches the device check, not the library
+        ops.cls_attn_pool(z(2, 5, 64), z(2, 3, 64), want_p=True)
+    with pytest.raises(ValueError, match="residual"):
+        ops.linear_splitk(z(2, 8), z(3, 8), None, residual=z(3, 2))
+    with pytest.raises(ValueError, match="ROCm"):
+        ops.linear_splitk(z(2, 8), z(3, 8), z(3), residual=z(2, 3))
+
+
+def test_registry_does_not_serve_the_token_aggregator_yet():
+    assert not [k for k in models.MODEL_REGISTRY if k.startswith("token")]
+    assert "token_r50" in models.OUT_OF_SCOPE and "token_r101" in models.OUT_OF_SCOPE
+    with pytest.raises(NotImplementedError):
+        models.get_model("token_r50", 10)
