@@ -73,7 +73,9 @@ typedef struct rr_handle_s* rr_handle_t;
  * rr_how_vlad and rr_how_asmk (the HOW head's aggregations), rr_sos_cov and
  * rr_linear_splitk (the SoSNet head: added, no existing entry changed),
  * rr_cls_attn_pool and rr_linear_splitk_ex (the token aggregator's folded last
- * layer: added, no existing entry changed), and the native
+ * layer: added, no existing entry changed), rr_spp_regions, rr_spp_max,
+ * rr_spoc_refine and rr_linear_groupmax (the SpoC head: added, no existing
+ * entry changed), and the native
  * trunk plan's rr_trunk_h2_* entries, rr_timing_collect_ex and the tuning key
  * RR_TUNE_TRUNK_PARTS (16); rr_timing_collect keeps its arguments and now
  * returns the UNION of the class's launch intervals (equal to the former sum
@@ -814,6 +816,69 @@ int rr_linear_splitk_ex(rr_handle_t h, const float* x, int m, int k,
 int rr_cls_attn_pool(rr_handle_t h, const float* x, int b, int seq, int d,
                      const float* qt, int heads, float* p, float* out,
                      void* stream);
+
+/* ---- SpoC head (models/spoc.py) ------------------------------------------ */
+/* The spatial pyramid of max-pools in one launch.  x [b][hgt][wid][c] NHWC
+ * fp32; levels [nlevels] is a HOST array read during the call.  Level L pools
+ * kh x kw = (hgt / L) x (wid / L) windows (integer division) at a stride equal
+ * to the window, no padding, floor mode: oh = hgt / kh, ow = wid / kw regions,
+ * and trailing rows and columns that fill no window are dropped.  Regions are
+ * row-major within a level and the levels follow one another, so out
+ * [b][R][c] is the reference's pyramid_features [B,C,R] with the region axis
+ * before the channels.  Replaces SpatialPyramidPooling.forward (:20-49,
+ * pool_type 'max': one F.max_pool2d, view and cat per level).
+ * The max starts from the window's first element (refined maps are signed);
+ * it is defined for finite inputs, like rr_stem_pool_h2's.  One workgroup per
+ * (image, region), 16-B loads along c.
+ * 1 <= nlevels <= 8, 1 <= level <= min(hgt, wid), c % 4 == 0, x and out 16-B
+ * aligned (else RR_EINVAL, nothing written); b == 0 is RR_OK and launches
+ * nothing; offsets are 64-bit.  Timing class 3.
+ * rr_spp_regions: R for (hgt, wid, levels), or -1 where rr_spp_max would
+ * refuse them (a level above hgt or wid: the reference raises "stride should
+ * not be zero").  Host only, no handle.                                     */
+int rr_spp_regions(int hgt, int wid, const int* levels, int nlevels);
+int rr_spp_max(rr_handle_t h, const float* x, int b, int hgt, int wid, int c,
+               const int* levels, int nlevels, float* out, void* stream);
+
+/* The gated refine conv.  With feature_refine's weight W = [Wx | Wc] split at
+ * the input width, per position m
+ *   a_m     = sigmoid(ctx_m . w_att + b_att)
+ *   y[m][:] = a_m u[m][:] + ctx_m w_c^T + bias
+ * u [m][c]: the RAW product Wx x_m from the conv core (no bias; the gate
+ * commutes with it, as in rr_sos_cov's a_p (Wp x_p)); ctx [m][dc]: the context
+ * encoder's output; w_att [dc], w_c [c][dc], bias [c]; att [m] (may be NULL)
+ * receives the a_m.  y may alias u: each element is read and written by the
+ * same thread.  Replaces ContextualAttention.forward's attention_conv +
+ * sigmoid (:83), the multiply (:86), the cat (:89) and feature_refine's
+ * context half and bias (:92): the attended map and the concatenation never
+ * exist.  The product over dc runs on the exact-fp32 MFMA in 64 x 64 tiles;
+ * the logit is computed inside the same kernel from the staged ctx rows, in
+ * an order that depends on dc alone, so every column tile of a row applies
+ * the same a_m bits; no scratch, the same bits on every run.
+ * dc % 32 == 0, 32 <= dc <= 2048; c % 4 == 0; m >= 0; every pointer 16-B
+ * aligned (else RR_EINVAL, nothing written); m == 0 is RR_OK and launches
+ * nothing.  Timing class 1.                                                  */
+int rr_spoc_refine(rr_handle_t h, const float* u, const float* ctx, int m,
+                   int c, int dc, const float* w_att, float b_att,
+                   const float* w_c, const float* bias, float* att, float* y,
+                   void* stream);
+
+/* A linear whose result is needed only as a per-image max over rows:
+ *   out[i][j] = max_{q < r} act(x[i r + q] . w[j] + bias[j]),
+ * x [b r][k], w [n][k], bias [n] (may be NULL), out [b][n]; act 0 none, 1 ReLU.
+ * Replaces feature_aggregation (:131-136: Conv1d(1) + BatchNorm1d folded into
+ * w and bias + ReLU + AdaptiveMaxPool1d(1)); the [b r][n] product never
+ * reaches global memory.  One image's r rows are the rows of one 64-row tile
+ * of the exact-fp32 MFMA; rows past r inside the tile are left out of the max
+ * (as zero rows they would give act(bias[j])), and the max starts at -inf.
+ * No split over k and no scratch: an image's result is the same bits alone
+ * or in a batch, on every run.
+ * 1 <= r <= 64; k % 4 == 0; n >= 1 (any n: stores are per element); b >= 0;
+ * every pointer 16-B aligned (else RR_EINVAL, nothing written); b == 0 is
+ * RR_OK and launches nothing.  Timing class 1.                               */
+int rr_linear_groupmax(rr_handle_t h, const float* x, int b, int r, int k,
+                       const float* w, const float* bias, int n, int act,
+                       float* out, void* stream);
 
 /* ---- native ResNet trunk plan (f16x2 core) -------------------------------
  * One call per forward for the whole bottleneck-ResNet trunk (torchvision

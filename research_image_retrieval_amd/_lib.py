@@ -107,6 +107,10 @@ SIGNATURES = {
     "rr_linear_splitk": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "rr_linear_splitk_ex": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "rr_cls_attn_pool": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "rr_spp_regions": (_i, [_i, _i, _vp, _i]),
+    "rr_spp_max": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "rr_spoc_refine": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
+    "rr_linear_groupmax": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "rr_linear_ex": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp]),
     "rr_layernorm": (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp, _f, _vp, _vp]),
     "rr_patchify": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

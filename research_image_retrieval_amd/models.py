@@ -15,6 +15,10 @@ The token aggregator (models/token_based.py:13-212) likewise: ``get_token_model(
 num_classes, backbone=..., hidden_dim=..., num_heads=..., num_layers=...)`` or
 ``TokenWrapper``, inputs up to 448 x 448 (196 positions); ``get_model('token_r50'
 | 'token_r101', ...)`` still raises NotImplementedError.
+SpoC (models/spoc.py:97-248) likewise: ``get_spoc_model(num_classes,
+backbone=..., pyramid_levels=..., context_dim=..., use_context=...)`` or
+``SpoCWrapper``; ``get_model('spoc_r50' | 'spoc_r101', ...)`` still raises
+NotImplementedError.
 Training (``forward(x, targets)`` losses, optimizers) is out of scope
 (SURVEY.md §2 row 13): ``forward`` only produces eval-mode logits.
 """
@@ -448,6 +452,184 @@ class SoSNetWrapper(_Extractor):
 
 def get_sosnet_model(num_classes, backbone="resnet50", **kwargs):
     return SoSNetWrapper(num_classes=num_classes, backbone=backbone, **kwargs)
+
+
+class SpoCModel(_Extractor):
+    """models/spoc.py:97-195, eval mode: resnet trunk -> ContextualAttention
+    (:52-94: two 3x3 convs with BN and ReLU to context_dim channels, a 1x1
+    attention conv with a sigmoid, and a 1x1 refine conv over cat[x a, ctx])
+    -> SpatialPyramidPooling (:12-49: max-pools with floor-mode windows at
+    pyramid_levels, the regions concatenated) -> feature_aggregation (Conv1d(1),
+    BatchNorm1d, ReLU, max over the regions) -> feature_proj (Linear, ReLU,
+    Dropout as a no-op, Linear); extract_descriptor adds F.normalize.
+
+    Launches after the trunk: the two 3x3 convs with their BNs folded and ReLU
+    (conv_math "h2": the f16x2 core, the first on the trunk's max-|x| record
+    and publishing the record the second reads; "f32": rr_conv2d); the 1x1
+    conv of feature_refine's input half Wx, RAW and without its bias, on the
+    same core; rr_spoc_refine in place on it (the attention conv, the sigmoid,
+    the gate, the context half Wc and the bias: refined_p = a_p (Wx x_p) +
+    Wc ctx_p + b); rr_spp_max; rr_linear_groupmax with ReLU (the [B R, F]
+    product stays on the chip); rr_linear_splitk with bias and ReLU, then
+    rr_linear_splitk without an activation (few rows at K = 2048, rr_linear's
+    K-set floor); rr_l2_normalize.  use_context=False goes from x4 straight to
+    rr_spp_max.
+
+    Constructor: the reference's (backbone, pretrained, num_classes,
+    feature_dim, pyramid_levels, context_dim, use_context), then state_dict
+    (trunk keys as networks.ResNet accepts, head keys as
+    weights.spoc_head_from_state_dict), seed (synthetic weights when state_dict
+    is None), device, conv_math and stride_on as GeMModel.  context_dim must be
+    a multiple of 32 in 32..2048 (rr_spoc_refine, and the f16x2 core's Cin).
+    At call time a map with H or W below the largest level raises, as the
+    reference does ("stride should not be zero"), and so do more than 64
+    regions (rr_linear_groupmax; the default levels give at most 54).
+
+    get_model("spoc_r50" | "spoc_r101") still raises NotImplementedError: the
+    names stay in OUT_OF_SCOPE and out of MODEL_REGISTRY (build the model with
+    get_spoc_model)."""
+
+    in_channels = 4
+
+    def __init__(self, backbone="resnet50", pretrained=False, num_classes=1000, feature_dim=2048,
+                 pyramid_levels=(1, 2, 4), context_dim=512, use_context=True, state_dict=None, seed=0, device="cuda",
+                 conv_math="h2", stride_on="3x3"):
+        if pretrained:
+            raise ValueError("pretrained weights need a download; pass a local state_dict instead "
+                             "(models/spoc.py:100 defaults to pretrained=True)")
+        if backbone not in ("resnet50", "resnet101"):
+            raise ValueError(f"Unsupported backbone: {backbone}")
+        dc = context_dim
+        if dc % 32 or not 32 <= dc <= 2048:
+            raise ValueError("SpoCModel: context_dim % 32 == 0, 32 <= context_dim <= 2048 (rr_spoc_refine)")
+        levels = [int(v) for v in pyramid_levels]
+        if not 1 <= len(levels) <= 8 or min(levels) < 1:
+            raise ValueError("SpoCModel: pyramid_levels must hold 1 to 8 levels, each >= 1 (rr_spp_max)")
+        if state_dict is None:
+            head = W.spoc_head_from_state_dict(W.synthetic_spoc_head(seed + 1, dc, num_classes, use_context,
+                                                                     feature_dim))
+        else:
+            head = W.spoc_head_from_state_dict(state_dict)
+        if ("ce0_w" in head) != bool(use_context):
+            raise ValueError("SpoCModel: use_context does not fit the state dict's head")
+        if head["agg_w"].shape[0] != feature_dim or (use_context and head["ce0_w"].shape[0] != dc):
+            raise ValueError("SpoCModel: head weight shapes do not fit feature_dim and context_dim")
+        self.device = torch.device(device)
+        self.conv_math = conv_math
+        self.use_context = bool(use_context)
+        self.pyramid_levels = levels
+        self.att_b = head.pop("att_b") if use_context else 0.0  # a python float, read before any device work
+        self.backbone = ResNet(backbone, state_dict, seed, device, conv_math=conv_math, stride_on=stride_on)
+        if head["agg_w"].shape[1] != self.backbone.outputdim_block5:
+            raise ValueError("SpoCModel: feature_aggregation does not fit the trunk")
+        self.w = {k: v.to(self.device) for k, v in head.items()}
+        self.h2 = {}
+        if use_context and conv_math == "h2":
+            self.h2 = {k: ops.H2Conv(self.w[k]) for k in ("ce0_w", "ce1_w", "refine_wx")}
+        self.context_dim, self.feature_dim = dc, feature_dim
+        self.outputdim = feature_dim
+
+    def _conv(self, x, x_amax, key, bias, pad, relu, y_amax=None):
+        if self.conv_math == "h2":
+            return ops.conv2d_h2(x, x_amax, self.h2[key], bias, 1, pad, None, relu, y_amax)
+        return ops.conv2d(x, self.w[key], bias, 1, pad, None, relu)
+
+    def head(self, x4, x4_amax=None, taps=None):
+        """x4 NHWC -> features [B,feature_dim] (:152-173).  taps: a dict that
+        receives att [B,N] (use_context), refined [B,H,W,C], pooled [B,R,C], agg
+        [B,F], hidden (after feature_proj's ReLU) and features (tests)."""
+        b, hgt, wid = x4.shape[0], x4.shape[1], x4.shape[2]
+        if hgt < max(self.pyramid_levels) or wid < max(self.pyramid_levels):
+            raise ValueError(f"SpoCModel: a {hgt} x {wid} map is below pyramid level {max(self.pyramid_levels)} (the "
+                             "reference's max_pool2d raises: stride should not be zero, models/spoc.py:27-35)")
+        regions = ops.spp_regions(hgt, wid, self.pyramid_levels)
+        if regions > 64:
+            raise ValueError(f"SpoCModel: {regions} pyramid regions on a {hgt} x {wid} map; rr_linear_groupmax takes "
+                             "at most 64 (the default levels give at most 54)")
+        att = None
+        refined = x4
+        if self.use_context:
+            c1_amax = None
+            if self.conv_math == "h2":
+                if x4_amax is None:
+                    x4_amax = ops.amax_f32(x4, ops.amax_records(1, x4.device)[0])
+                c1_amax = ops.amax_records(1, x4.device)[0]
+            c1 = self._conv(x4, x4_amax, "ce0_w", self.w["ce0_b"], 1, True, c1_amax)
+            ctx = self._conv(c1, c1_amax, "ce1_w", self.w["ce1_b"], 1, True)
+            u = self._conv(x4, x4_amax, "refine_wx", None, 0, False)
+            got = ops.spoc_refine(u, ctx, self.w["att_w"], self.att_b, self.w["refine_wc"], self.w["refine_b"],
+                                  want_att=taps is not None, out=u)
+            refined, att = got if taps is not None else (got, None)
+        pooled = ops.spp_max(refined, self.pyramid_levels)
+        agg = ops.linear_groupmax(pooled, self.w["agg_w"], self.w["agg_b"], act=1)
+        hidden = ops.linear_splitk(agg, self.w["fp0_w"], self.w["fp0_b"], act=1)
+        f = ops.linear_splitk(hidden, self.w["fp3_w"], self.w["fp3_b"])
+        if taps is not None:
+            taps.update(att=None if att is None else att.view(b, hgt * wid), refined=refined, pooled=pooled, agg=agg,
+                        hidden=hidden, features=f)
+        return f
+
+    def _trunk(self, x_nhwc, hook=None):
+        if self.conv_math == "h2":
+            return self.backbone(x_nhwc, hook=hook, return_amax=True)
+        return self.backbone(x_nhwc), None
+
+    def extract_features_nhwc(self, x_nhwc, hook=None):
+        return self.head(*self._trunk(x_nhwc, hook))
+
+    @torch.no_grad()
+    def extract_features(self, x):
+        return self.extract_features_nhwc(self._input(x))
+
+    def forward_test_nhwc(self, x_nhwc, hook=None):
+        f = self.extract_features_nhwc(x_nhwc, hook)
+        return ops.l2_normalize(f, EPS_L2, out=f)
+
+    @torch.no_grad()
+    def extract_descriptor(self, x):
+        return self.forward_test(x)
+
+    @torch.no_grad()
+    def forward(self, x, targets=None):
+        feats = self.extract_features(x)
+        return None, ops.linear(feats, self.w["cls_w"], self.w["cls_b"])
+
+    __call__ = forward
+
+
+class SpoCWrapper(_Extractor):
+    """models/spoc.py:198-225: training-loop facade over SpoCModel."""
+
+    in_channels = 4
+
+    def __init__(self, num_classes, backbone="resnet50", feature_dim=2048, pyramid_levels=(1, 2, 4), context_dim=512,
+                 use_context=True, **kw):
+        self.backbone = SpoCModel(backbone=backbone, num_classes=num_classes, feature_dim=feature_dim,
+                                  pyramid_levels=pyramid_levels, context_dim=context_dim, use_context=use_context,
+                                  **kw)
+        self.outputdim = self.backbone.outputdim
+
+    def forward_test_nhwc(self, x_nhwc, hook=None):
+        return self.backbone.forward_test_nhwc(x_nhwc, hook)
+
+    @torch.no_grad()
+    def forward(self, x, targets=None):
+        return self.backbone(x)
+
+    __call__ = forward
+
+    def extract_features(self, x):
+        return self.backbone.extract_features(x)
+
+    def extract_descriptor(self, x):
+        return self.backbone.extract_descriptor(x)
+
+    def extract_global_descriptor(self, x):
+        return self.backbone.extract_descriptor(x)
+
+
+def get_spoc_model(num_classes, backbone="resnet50", **kwargs):
+    return SpoCWrapper(num_classes=num_classes, backbone=backbone, **kwargs)
 
 
 class TokenModel(_Extractor):

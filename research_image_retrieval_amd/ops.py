@@ -698,6 +698,117 @@ def cls_attn_pool(x, qt, want_p=False):
     return (out, p) if want_p else out
 
 
+def _levels(levels, name):
+    lv = [int(v) for v in levels]
+    if not 1 <= len(lv) <= 8 or any(v < 1 for v in lv):
+        raise ValueError(f"{name}: 1 <= len(levels) <= 8, every level >= 1")
+    return (ctypes.c_int * len(lv))(*lv), len(lv)
+
+
+def spp_regions(hgt, wid, levels):
+    """Regions of the reference's max-pool pyramid on an hgt x wid map
+    (rr_spp_regions): per level L, (hgt // (hgt // L)) * (wid // (wid // L));
+    ValueError where a level is above hgt or wid (the reference raises "stride
+    should not be zero")."""
+    arr, n = _levels(levels, "spp_regions")
+    r = _lib.lib().rr_spp_regions(int(hgt), int(wid), ctypes.cast(arr, ctypes.c_void_p), n)
+    if r < 0:
+        raise ValueError(f"spp_regions: a level of {list(levels)} is above the {hgt} x {wid} map (the reference's "
+                         "max_pool2d raises: stride should not be zero)")
+    return r
+
+
+def spp_max(x_nhwc, levels):
+    """SpoC's spatial pyramid of max-pools (rr_spp_max): x NHWC [B,H,W,C],
+    C % 4 == 0 -> pooled [B,R,C], regions in the reference's order (row-major
+    per level, the levels one after another; floor-mode windows)."""
+    _f32(x_nhwc, "spp_max x")
+    if x_nhwc.dim() != 4:
+        raise ValueError(f"spp_max: x [B,H,W,C], got {tuple(x_nhwc.shape)}")
+    b, h, w, c = x_nhwc.shape
+    if c % 4 or c == 0:
+        raise ValueError("spp_max: c % 4 == 0, c > 0")
+    arr, n = _levels(levels, "spp_max")
+    r = spp_regions(h, w, levels)
+    dev = _dev(x_nhwc)
+    out = torch.empty((b, r, c), dtype=torch.float32, device=x_nhwc.device)
+    if b:
+        hd = _lib.handle(dev)
+        _lib.check(_lib.lib().rr_spp_max(hd, _ptr(x_nhwc), b, h, w, c, ctypes.cast(arr, ctypes.c_void_p), n, _ptr(out),
+                                         _stream(dev)), hd, "rr_spp_max")
+    return out
+
+
+def spoc_refine(u, ctx, w_att, b_att, w_c, bias, want_att=False, out=None):
+    """SpoC's gated refine (rr_spoc_refine): u [M,C] (or NHWC), the RAW product
+    Wx x of feature_refine's input half WITHOUT its bias; ctx [M,DC] (or NHWC),
+    the context encoder's output; w_att [DC] and b_att (python float) the
+    attention conv; w_c [C,DC] feature_refine's context half, bias [C] ->
+    y = sigmoid(ctx . w_att + b_att)[:, None] * u + ctx @ w_c.T + bias, shaped
+    as u, and att [M] as a second value with want_att.  out: None (a new
+    tensor) or u itself (in place)."""
+    _f32(u, "spoc_refine u")
+    _f32(ctx, "spoc_refine ctx")
+    _f32(w_att, "spoc_refine w_att")
+    _f32(w_c, "spoc_refine w_c")
+    _f32(bias, "spoc_refine bias")
+    if u.dim() < 2 or ctx.dim() < 2:
+        raise ValueError(f"spoc_refine: u [M,C] and ctx [M,DC], got {tuple(u.shape)} and {tuple(ctx.shape)}")
+    c, dc = u.shape[-1], ctx.shape[-1]
+    if dc % 32 or not 32 <= dc <= 2048:
+        raise ValueError("spoc_refine: dc % 32 == 0, 32 <= dc <= 2048")
+    if c % 4 or c == 0:
+        raise ValueError("spoc_refine: c % 4 == 0, c > 0")
+    m = u.numel() // c
+    if ctx.numel() != m * dc or tuple(ctx.shape[:-1]) != tuple(u.shape[:-1]):
+        raise ValueError(f"spoc_refine: ctx must hold u's rows, got {tuple(u.shape)} and {tuple(ctx.shape)}")
+    if w_att.numel() != dc or tuple(w_c.shape) != (c, dc) or bias.numel() != c:
+        raise ValueError(f"spoc_refine: w_att [{dc}], w_c [{c},{dc}] and bias [{c}], got {tuple(w_att.shape)}, "
+                         f"{tuple(w_c.shape)} and {tuple(bias.shape)}")
+    if out is not None and out is not u:
+        raise ValueError("spoc_refine: out must be None or u itself")
+    if any(t.device != u.device for t in (ctx, w_att, w_c, bias)):
+        raise ValueError("spoc_refine: every tensor must be on one device")
+    dev = _dev(u)
+    y = u if out is u else torch.empty_like(u)
+    att = torch.empty((m,), dtype=torch.float32, device=u.device) if want_att else None
+    if m:
+        hd = _lib.handle(dev)
+        _lib.check(_lib.lib().rr_spoc_refine(hd, _ptr(u), _ptr(ctx), m, c, dc, _ptr(w_att), float(b_att), _ptr(w_c),
+                                             _ptr(bias), _ptr(att), _ptr(y), _stream(dev)), hd, "rr_spoc_refine")
+    return (y, att) if want_att else y
+
+
+def linear_groupmax(x, w, bias, act=0):
+    """out[i] = max over image i's rows of act(x[i] @ w.T + bias)
+    (rr_linear_groupmax): x [B,R,K] with 1 <= R <= 64 and K % 4 == 0, w [N,K],
+    bias [N] or None, act 0 none / 1 ReLU -> [B,N]; the [B,R,N] product never
+    reaches memory."""
+    _f32(x, "linear_groupmax x")
+    _f32(w, "linear_groupmax w")
+    if x.dim() != 3 or w.dim() != 2 or w.shape[1] != x.shape[2]:
+        raise ValueError(f"linear_groupmax: x [B,R,K] and w [N,K], got {tuple(x.shape)} and {tuple(w.shape)}")
+    b, r, k = x.shape
+    n = w.shape[0]
+    if not 1 <= r <= 64:
+        raise ValueError("linear_groupmax: 1 <= r <= 64 rows per image")
+    if k % 4 or k == 0 or n == 0:
+        raise ValueError("linear_groupmax: k % 4 == 0, k > 0, n > 0")
+    if bias is not None and (_f32(bias, "linear_groupmax bias").numel() != n or bias.device != x.device):
+        raise ValueError(f"linear_groupmax: bias must be [{n}] on x's device")
+    if int(act) not in (0, 1):
+        raise ValueError("linear_groupmax: act must be 0 or 1")
+    if w.device != x.device:
+        raise ValueError("linear_groupmax: x and w must be on one device")
+    dev = _dev(x)
+    out = torch.empty((b, n), dtype=torch.float32, device=x.device)
+    if b:
+        hd = _lib.handle(dev)
+        _lib.check(_lib.lib().rr_linear_groupmax(hd, _ptr(x), b, r, k, _ptr(w), _ptr(bias), n, int(act), _ptr(out),
+                                                 _stream(dev)), hd, "rr_linear_groupmax")
+    return out
+
+
 def gelu(x, out=None):
     """Exact (erf) GELU (rr_gelu), elementwise; out=x runs in place."""
     _f32(x, "gelu")

@@ -501,6 +501,157 @@ def synthetic_sos_head(seed, second_order_dim=512, num_classes=8, use_attention=
     return sd
 
 
+# ---- SpoC head (models/spoc.py:52-147) --------------------------------------
+_BN_KEYS = ("weight", "bias", "running_mean", "running_var")
+_CA = "contextual_attention."
+SPOC_CTX_KEYS = tuple(f"{_CA}context_encoder.{i}.{k}" for i in (0, 3) for k in ("weight", "bias")) + \
+    tuple(f"{_CA}context_encoder.{i}.{k}" for i in (1, 4) for k in _BN_KEYS) + \
+    tuple(f"{_CA}{n}.{k}" for n in ("attention_conv", "feature_refine") for k in ("weight", "bias"))
+SPOC_HEAD_KEYS = ("feature_aggregation.0.weight", "feature_aggregation.0.bias") + \
+    tuple(f"feature_aggregation.1.{k}" for k in _BN_KEYS) + \
+    ("feature_proj.0.weight", "feature_proj.0.bias", "feature_proj.3.weight", "feature_proj.3.bias",
+     "classifier.weight", "classifier.bias")
+SPOC_ATT_GAIN = 32.0  # synthetic_spoc_head: the attention conv's gain over PyTorch's default init
+
+
+def _fold_bn_biased(w, conv_b, flat, bn, eps):
+    """Eval-mode BN `bn`.* of flat folded into a conv / linear WITH its own
+    bias: (w * scale per output row, (b_conv - mean) * scale + beta), in
+    float64; fold_bn assumes a bias-free conv."""
+    g, b, m, v = (flat[f"{bn}.{k}"].double() for k in _BN_KEYS)
+    for k in _BN_KEYS:
+        if tuple(flat[f"{bn}.{k}"].shape) != (w.shape[0],):
+            raise ValueError(f"{bn}.{k}: expected [{w.shape[0]}], got {tuple(flat[f'{bn}.{k}'].shape)}")
+    scale = g / torch.sqrt(v + eps)
+    return w.double() * scale.reshape(-1, *([1] * (w.dim() - 1))), (conv_b.double() - m) * scale + b
+
+
+def spoc_head_from_state_dict(sd, eps=BN_EPS):
+    """The SpoC head of a reference checkpoint (SpoCModel's keys
+    contextual_attention.context_encoder.{0,1,3,4}.*, .attention_conv.*,
+    .feature_refine.*, feature_aggregation.{0,1}.*, feature_proj.{0,3}.*,
+    classifier.*, bare or under the wrapper's leading ``backbone.``, a
+    ``module.`` before either dropped; trunk keys are ignored) as fp32
+    contiguous tensors, every BN folded in float64 WITH the conv's own bias
+    and rounded once:
+
+      ce0_w [Dc,3,3,Cin] and ce1_w [Dc,3,3,Dc] NHWC-ready, ce0_b, ce1_b [Dc];
+      att_w [Dc], att_b (a python float); refine_wx [C,1,1,Cin] and refine_wc
+      [C,Dc], feature_refine's weight split at column Cin, refine_b [C] (the
+      contextual_attention keys absent together: use_context=False);
+      agg_w [F,C], agg_b [F] (Conv1d(1) + BatchNorm1d); fp0_w [F,F], fp0_b,
+      fp3_w [F,F], fp3_b; cls_w [classes,F], cls_b."""
+    flat = {}
+    for k, v in sd.items():
+        for lead in ("module.", "backbone."):
+            if k.startswith(lead):
+                k = k[len(lead):]
+        flat.setdefault(k, v)
+    missing = [k for k in SPOC_HEAD_KEYS if k not in flat]
+    have_ctx = [k for k in SPOC_CTX_KEYS if k in flat]
+    if have_ctx and len(have_ctx) != len(SPOC_CTX_KEYS):
+        missing += [k for k in SPOC_CTX_KEYS if k not in flat]
+    if missing:
+        raise ValueError(f"SpoC head: missing keys {missing}")
+    f = lambda a: a.float().contiguous()  # noqa: E731
+    aw, f0, f3, cw = (flat[k] for k in ("feature_aggregation.0.weight", "feature_proj.0.weight",
+                                        "feature_proj.3.weight", "classifier.weight"))
+    if aw.dim() != 3 or aw.shape[2] != 1:
+        raise ValueError(f"feature_aggregation.0.weight: expected [F,C,1], got {tuple(aw.shape)}")
+    fd, c = aw.shape[0], aw.shape[1]
+    if tuple(f0.shape) != (fd, fd):
+        raise ValueError(f"feature_proj.0.weight: expected [{fd},{fd}], got {tuple(f0.shape)}")
+    if tuple(f3.shape) != (fd, fd):
+        raise ValueError(f"feature_proj.3.weight: expected [{fd},{fd}], got {tuple(f3.shape)}")
+    if cw.dim() != 2 or cw.shape[1] != fd:
+        raise ValueError(f"classifier.weight: expected [classes,{fd}], got {tuple(cw.shape)}")
+    for k, n in (("feature_aggregation.0.bias", fd), ("feature_proj.0.bias", fd), ("feature_proj.3.bias", fd),
+                 ("classifier.bias", cw.shape[0])):
+        if tuple(flat[k].shape) != (n,):
+            raise ValueError(f"{k}: expected [{n}], got {tuple(flat[k].shape)}")
+    wa, ba = _fold_bn_biased(aw.reshape(fd, c), flat["feature_aggregation.0.bias"], flat, "feature_aggregation.1", eps)
+    head = {"agg_w": f(wa), "agg_b": f(ba), "fp0_w": f(f0), "fp0_b": f(flat["feature_proj.0.bias"]), "fp3_w": f(f3),
+            "fp3_b": f(flat["feature_proj.3.bias"]), "cls_w": f(cw), "cls_b": f(flat["classifier.bias"])}
+    if have_ctx:
+        enc = _CA + "context_encoder."
+        w0, w1 = flat[enc + "0.weight"], flat[enc + "3.weight"]
+        if w0.dim() != 4 or tuple(w0.shape[1:]) != (c, 3, 3):
+            raise ValueError(f"{enc}0.weight: expected [Dc,{c},3,3], got {tuple(w0.shape)}")
+        dc = w0.shape[0]
+        if tuple(w1.shape) != (dc, dc, 3, 3):
+            raise ValueError(f"{enc}3.weight: expected [{dc},{dc},3,3], got {tuple(w1.shape)}")
+        wt, wr = flat[_CA + "attention_conv.weight"], flat[_CA + "feature_refine.weight"]
+        if tuple(wt.shape) != (1, dc, 1, 1) or flat[_CA + "attention_conv.bias"].numel() != 1:
+            raise ValueError(f"{_CA}attention_conv: expected weight [1,{dc},1,1] and bias [1], got {tuple(wt.shape)} "
+                             f"and {tuple(flat[_CA + 'attention_conv.bias'].shape)}")
+        if tuple(wr.shape) != (c, c + dc, 1, 1) or tuple(flat[_CA + "feature_refine.bias"].shape) != (c,):
+            raise ValueError(f"{_CA}feature_refine: expected weight [{c},{c + dc},1,1] and bias [{c}], got "
+                             f"{tuple(wr.shape)} and {tuple(flat[_CA + 'feature_refine.bias'].shape)}")
+        for i in (0, 3):
+            if tuple(flat[f"{enc}{i}.bias"].shape) != (dc,):
+                raise ValueError(f"{enc}{i}.bias: expected [{dc}], got {tuple(flat[f'{enc}{i}.bias'].shape)}")
+        wf0, bf0 = _fold_bn_biased(w0, flat[enc + "0.bias"], flat, enc + "1", eps)
+        wf1, bf1 = _fold_bn_biased(w1, flat[enc + "3.bias"], flat, enc + "4", eps)
+        wr2 = wr.reshape(c, c + dc)
+        head.update(ce0_w=f(wf0.permute(0, 2, 3, 1)), ce0_b=f(bf0), ce1_w=f(wf1.permute(0, 2, 3, 1)), ce1_b=f(bf1),
+                    att_w=f(wt.reshape(dc)), att_b=float(flat[_CA + "attention_conv.bias"].reshape(())),
+                    refine_wx=f(wr2[:, :c]).reshape(c, 1, 1, c), refine_wc=f(wr2[:, c:]),
+                    refine_b=f(flat[_CA + "feature_refine.bias"]))
+    return head
+
+
+def synthetic_spoc_head(seed, context_dim=512, num_classes=8, use_context=True, feature_dim=2048):
+    """Seeded SpoC head weights under SpoCModel's keys (SPOC_CTX_KEYS with
+    use_context, SPOC_HEAD_KEYS), each Conv / Linear drawn as PyTorch's default
+    init, U(+-1 / sqrt(fan_in)) — except the attention conv, whose weights are
+    drawn SPOC_ATT_GAIN times wider and shifted to sum to zero (its bias is not
+    widened): ctx is post-ReLU, so this is synthetic_sos_head's problem and its
+    cure — with the default init a stays near 0.5 and a head that ignored the
+    gate would pass; weights that do not sum to zero push every logit one way.
+    The logits' centre still moves with the seed (the channels' means differ),
+    so a fixture picks a seed at which a spans [<= 0.2, >= 0.8] on its maps
+    (tests/golden/make_golden_spoc.py asserts it).  The BatchNorms get
+    non-trivial statistics (gamma and variance in U(0.5, 1.5), beta and mean
+    N(0, 0.1)); the folded aggregation bias is then of the size of the
+    pre-activations, and ReLU clips every region in some columns (an exact 0
+    in agg, the pad-row trap of rr_linear_groupmax)."""
+    rs = np.random.RandomState(seed)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
+    sd = collections.OrderedDict()
+    c = 2048
+
+    def lin(key, out_dim, in_dim, shape=None, gain=1.0, zero_sum=False):
+        s = 1.0 / np.sqrt(in_dim)
+        w = np.empty((out_dim, in_dim), dtype=np.float32)
+        for r0 in range(0, out_dim, 64):  # row blocks: the float64 draws of the 3x3 convs stay small
+            blk = rs.uniform(-1, 1, (min(64, out_dim - r0), in_dim)) * (s * gain)
+            w[r0:r0 + 64] = blk - blk.mean(axis=1, keepdims=True) if zero_sum else blk
+        sd[key + ".weight"] = t(w.reshape(shape) if shape else w)
+        sd[key + ".bias"] = t(rs.uniform(-1, 1, out_dim) * s)
+
+    def bn(key, n):
+        sd[key + ".weight"] = t(rs.uniform(0.5, 1.5, n))
+        sd[key + ".bias"] = t(rs.standard_normal(n) * 0.1)
+        sd[key + ".running_mean"] = t(rs.standard_normal(n) * 0.1)
+        sd[key + ".running_var"] = t(rs.uniform(0.5, 1.5, n))
+
+    dc = context_dim
+    if use_context:
+        enc = _CA + "context_encoder."
+        lin(enc + "0", dc, c * 9, shape=(dc, c, 3, 3))
+        bn(enc + "1", dc)
+        lin(enc + "3", dc, dc * 9, shape=(dc, dc, 3, 3))
+        bn(enc + "4", dc)
+        lin(_CA + "attention_conv", 1, dc, shape=(1, dc, 1, 1), gain=SPOC_ATT_GAIN, zero_sum=True)
+        lin(_CA + "feature_refine", c, c + dc, shape=(c, c + dc, 1, 1))
+    lin("feature_aggregation.0", feature_dim, c, shape=(feature_dim, c, 1))
+    bn("feature_aggregation.1", feature_dim)
+    lin("feature_proj.0", feature_dim, feature_dim)
+    lin("feature_proj.3", feature_dim, feature_dim)
+    lin("classifier", num_classes, feature_dim)
+    return sd
+
+
 # ---- token aggregator head (models/token_based.py:13-159) -------------------
 # (networks.Token / token_head_from_state_dict below are the OTHER token model,
 # networks/RetrievalNet.py's Token_Refine.)
