@@ -26,203 +26,53 @@ import torch
 
 from . import ops
 from . import weights as W
-from .networks import ResNet, _Extractor, EPS_L2
+from .networks import ResNet, HeadConv, _Extractor, EPS_L2
 
 
-class GeMPooling:
-    """GeM with a tensor-valued p (models/gem_pooling.py:12-23).  The
-    reference stores p as a 1-element Parameter; the exponent 1/p is formed
-    in fp32 from it, which is what gem_pool's powf path does."""
-
-    def __init__(self, p=3.0, eps=1e-6):
-        self.p = torch.ones(1) * p
-        self.eps = eps
-
-    def __call__(self, x_nhwc):
-        return ops.gem_pool(x_nhwc, float(self.p.item()), self.eps)
-
-
-class GeMModel(_Extractor):
-    """resnet trunk -> GeMPooling -> feature_proj Linear(2048, feature_dim)
-    (models/gem_pooling.py:26-92); extract_descriptor adds F.normalize(p=2, dim=1)."""
+class _TrunkHeadModel(_Extractor):
+    """A Table-1 model: a networks.ResNet trunk in self.backbone and a head on
+    the trunk's last map.  A subclass's __init__ calls, in this order,
+    _check_backbone, its own argument checks, _load_head, its own head-shape
+    checks and host-side reads, and _build, where the device work starts; it
+    defines head(x4, x4_amax=None) -> features [B,outputdim].  self.w holds the
+    head's tensors on the device under the loader's keys, cls_w and cls_b among
+    them.  _Extractor._trunk() stays None: forward_test_u8 preprocesses and
+    calls forward_test_nhwc, it does not run the trunk as the native plan."""
 
     in_channels = 4
 
-    def __init__(self, backbone="resnet50", pretrained=False, num_classes=1000, feature_dim=2048, gem_p=3.0,
-                 state_dict=None, seed=0, device="cuda", conv_math="h2", stride_on="3x3"):
+    @staticmethod
+    def _check_backbone(pretrained, backbone, cite):
+        """cite: where the reference's constructor defaults to pretrained=True."""
         if pretrained:
             raise ValueError("pretrained weights need a download; pass a local state_dict instead "
-                             "(models/gem_pooling.py:35 defaults to pretrained=True)")
+                             f"({cite} defaults to pretrained=True)")
         if backbone not in ("resnet50", "resnet101"):
             raise ValueError(f"Unsupported backbone: {backbone}")
-        self.device = torch.device(device)
-        self.backbone = ResNet(backbone, state_dict, seed, device, conv_math=conv_math, stride_on=stride_on)
-        self.gem_pool = GeMPooling(p=gem_p)
-        backbone_dim = 2048
-        pw, pb = _from_sd(state_dict, "feature_proj") or W.synthetic_linear(feature_dim, backbone_dim, seed + 2)
-        self.proj_w = pw.float().contiguous().to(self.device)
-        self.proj_b = pb.float().contiguous().to(self.device)
-        cw, cb = _from_sd(state_dict, "classifier") or W.synthetic_linear(num_classes, feature_dim, seed + 3)
-        self.cls_w = cw.float().contiguous().to(self.device)
-        self.cls_b = cb.float().contiguous().to(self.device)
-        self.feature_dim = feature_dim
-        self.outputdim = feature_dim
 
-    def extract_features_nhwc(self, x_nhwc):
-        f = self.backbone(x_nhwc)
-        f = self.gem_pool(f)
-        return ops.linear(f, self.proj_w, self.proj_b)
+    @staticmethod
+    def _load_head(state_dict, seed, from_sd, synthetic, *args):
+        """from_sd of the state dict, or of synthetic(seed + 1, *args) when there is none."""
+        return from_sd(synthetic(seed + 1, *args) if state_dict is None else state_dict)
 
-    @torch.no_grad()
-    def extract_features(self, x):
-        return self.extract_features_nhwc(self._input(x))
-
-    def forward_test_nhwc(self, x_nhwc):
-        f = self.extract_features_nhwc(x_nhwc)
-        return ops.l2_normalize(f, EPS_L2, out=f)
-
-    @torch.no_grad()
-    def extract_descriptor(self, x):
-        return self.forward_test(x)
-
-    @torch.no_grad()
-    def forward(self, x, targets=None):
-        feats = self.extract_features(x)
-        return None, ops.linear(feats, self.cls_w, self.cls_b)
-
-    __call__ = forward
-
-
-def _from_sd(sd, name):
-    if sd is None:
-        return None
-    for pre in ("", "backbone.", "module.backbone."):
-        k = f"{pre}{name}.weight"
-        if k in sd:
-            return sd[k], sd[f"{pre}{name}.bias"]
-    return None
-
-
-class GeMWrapper(_Extractor):
-    """models/gem_pooling.py:95-119: training-loop facade over GeMModel."""
-
-    in_channels = 4
-
-    def __init__(self, num_classes, backbone="resnet50", feature_dim=2048, gem_p=3.0, **kw):
-        self.backbone = GeMModel(backbone=backbone, num_classes=num_classes, feature_dim=feature_dim, gem_p=gem_p,
-                                 **kw)
-        self.outputdim = feature_dim
-
-    def forward_test_nhwc(self, x_nhwc):
-        return self.backbone.forward_test_nhwc(x_nhwc)
-
-    @torch.no_grad()
-    def forward(self, x, targets=None):
-        return self.backbone(x)
-
-    __call__ = forward
-
-    @torch.no_grad()
-    def extract_global_descriptor(self, x):
-        return self.backbone.extract_descriptor(x)
-
-
-def get_gem_model(num_classes, backbone="resnet50", **kwargs):
-    return GeMWrapper(num_classes=num_classes, backbone=backbone, **kwargs)
-
-
-class HOWModel(_Extractor):
-    """models/how_vlad.py:107-199, eval mode: resnet trunk -> local_proj (1x1
-    conv 2048 -> local_dim, +bias) -> F.normalize per position -> VLADPooling
-    (alpha = 100) or ASMKPooling -> final_proj Linear(K D or K, 2048);
-    extract_descriptor adds F.normalize.
-
-    Launches after the trunk: the 1x1 conv (conv_math "h2": the f16x2 core on
-    the trunk's max-|x| record; "f32": rr_conv2d), rr_how_vlad or rr_how_asmk on
-    its RAW rows (the per-position normalisation, the distances, the assignment
-    and the aggregation in one read), rr_l2_normalize over the pooled vector
-    (:56, :102), rr_linear, rr_l2_normalize.
-
-    Constructor: the reference's (backbone, pretrained, num_classes, local_dim,
-    pooling_type, num_clusters), then state_dict (trunk keys as networks.ResNet
-    accepts, the reference's index-named nn.Sequential keys included; head
-    keys as weights.how_head_from_state_dict), seed (synthetic weights when
-    state_dict is None), device, conv_math and stride_on as GeMModel."""
-
-    in_channels = 4
-    alpha = 100.0  # VLADPooling's default (:17); HOWModel never passes another
-
-    def __init__(self, backbone="resnet50", pretrained=False, num_classes=1000, local_dim=128, pooling_type="vlad",
-                 num_clusters=64, state_dict=None, seed=0, device="cuda", conv_math="h2", stride_on="3x3"):
-        if pretrained:
-            raise ValueError("pretrained weights need a download; pass a local state_dict instead "
-                             "(models/how_vlad.py:110 defaults to pretrained=True)")
-        if backbone not in ("resnet50", "resnet101"):
-            raise ValueError(f"Unsupported backbone: {backbone}")
-        if pooling_type not in ("vlad", "asmk"):
-            raise ValueError(f"Unsupported pooling type: {pooling_type}")
-        if local_dim % 32 or not 32 <= local_dim <= 256 or not 1 <= num_clusters <= 128:
-            raise ValueError("HOWModel: local_dim % 32 == 0, 32 <= local_dim <= 256, 1 <= num_clusters <= 128 "
-                             "(rr_how_vlad / rr_how_asmk)")
-        if state_dict is None:
-            head = W.how_head_from_state_dict(W.synthetic_how_head(seed + 1, pooling_type, local_dim, num_clusters,
-                                                                   num_classes))
-        else:
-            head = W.how_head_from_state_dict(state_dict)
-        if ("weights" in head) != (pooling_type == "asmk"):
-            raise ValueError(f"HOWModel: the state dict's head is not a {pooling_type} head")
-        if tuple(head["centroids"].shape) != (num_clusters, local_dim) or head["final_w"].shape[0] != 2048:
-            raise ValueError("HOWModel: head weight shapes do not fit local_dim and num_clusters")
+    def _build(self, head, fit, backbone, state_dict, seed, device, conv_math, stride_on):
+        """The trunk, then the head's tensors on its device.  fit: (key, the
+        reference's name) of the head weight whose columns are the trunk's
+        channels, or None."""
         self.device = torch.device(device)
         self.conv_math = conv_math
-        self.pooling_type = pooling_type
         self.backbone = ResNet(backbone, state_dict, seed, device, conv_math=conv_math, stride_on=stride_on)
-        if head["local_w"].shape[1] != self.backbone.outputdim_block5:
-            raise ValueError("HOWModel: local_proj does not fit the trunk")
+        if fit is not None and head[fit[0]].shape[1] != self.backbone.outputdim_block5:
+            raise ValueError(f"{type(self).__name__}: {fit[1]} does not fit the trunk")
         self.w = {k: v.to(self.device) for k, v in head.items()}
-        self.local_w = self.w["local_w"].view(local_dim, 1, 1, -1)
-        self.local_h2 = ops.H2Conv(self.local_w) if conv_math == "h2" else None
-        self.local_dim, self.num_clusters = local_dim, num_clusters
-        self.outputdim = 2048
 
-    def local_map(self, x4, x4_amax=None):
-        """The raw local_proj output [B,H,W,local_dim] of a trunk map x4 NHWC."""
-        if self.conv_math == "h2":
-            if x4_amax is None:
-                x4_amax = ops.amax_f32(x4, ops.amax_records(1, x4.device)[0])
-            return ops.conv2d_h2(x4, x4_amax, self.local_h2, self.w["local_b"], 1, 0, None, False)
-        return ops.conv2d(x4, self.local_w, self.w["local_b"], 1, 0, None, False)
-
-    def head(self, x4, x4_amax=None, taps=None):
-        """x4 NHWC -> features [B,2048] (:155-175).  taps: a dict that receives
-        local (the raw local_proj rows [B,N,D]), pooled (after its L2) and
-        features (tests)."""
-        y = self.local_map(x4, x4_amax)
-        if self.pooling_type == "vlad":
-            v = ops.how_vlad(y, self.w["centroids"], self.alpha)
-        else:
-            v = ops.how_asmk(y, self.w["centroids"], self.w["weights"])
-        v = ops.l2_normalize(v, EPS_L2, out=v)
-        f = ops.linear(v, self.w["final_w"], self.w["final_b"])
-        if taps is not None:
-            taps.update(local=y.view(y.shape[0], -1, y.shape[-1]), pooled=v, features=f)
-        return f
-
-    def _trunk(self, x_nhwc, hook=None):
-        if self.conv_math == "h2":
-            return self.backbone(x_nhwc, hook=hook, return_amax=True)
-        return self.backbone(x_nhwc), None
+    def trunk_map(self, x_nhwc, hook=None):
+        """NHWC pixels -> (x4, x4's max-|x| record; None on the "f32" trunk)."""
+        _, x4, _, x4_amax = self.backbone.maps(x_nhwc, hook)
+        return x4, x4_amax
 
     def extract_features_nhwc(self, x_nhwc, hook=None):
-        return self.head(*self._trunk(x_nhwc, hook))
-
-    @torch.no_grad()
-    def extract_local_descriptors(self, x):
-        """L2-normalised local descriptors [B,N,D] (:149-164), for callers: the
-        pooling kernels normalise on load and never write these."""
-        y = self.local_map(*self._trunk(self._input(x)))
-        b, d = y.shape[0], y.shape[-1]
-        return ops.l2_normalize(y.view(-1, d), EPS_L2).view(b, -1, d)
+        return self.head(*self.trunk_map(x_nhwc, hook))
 
     @torch.no_grad()
     def extract_features(self, x):
@@ -241,19 +91,19 @@ class HOWModel(_Extractor):
         feats = self.extract_features(x)
         return None, ops.linear(feats, self.w["cls_w"], self.w["cls_b"])
 
-    __call__ = forward
+    def __call__(self, x, targets=None):
+        return self.forward(x, targets)
 
 
-class _HOWWrapper(_Extractor):
-    """models/how_vlad.py:202-255: training-loop facade over HOWModel."""
+class _Wrapper(_Extractor):
+    """The reference's training-loop facade over a _TrunkHeadModel, kept in
+    self.backbone as the reference's wrappers keep theirs."""
 
     in_channels = 4
-    pooling_type = None
 
-    def __init__(self, num_classes, backbone="resnet50", local_dim=128, num_clusters=64, **kw):
-        self.backbone = HOWModel(backbone=backbone, num_classes=num_classes, local_dim=local_dim,
-                                 pooling_type=self.pooling_type, num_clusters=num_clusters, **kw)
-        self.outputdim = self.backbone.outputdim
+    def __init__(self, model):
+        self.backbone = model
+        self.outputdim = model.outputdim
 
     def forward_test_nhwc(self, x_nhwc, hook=None):
         return self.backbone.forward_test_nhwc(x_nhwc, hook)
@@ -262,10 +112,8 @@ class _HOWWrapper(_Extractor):
     def forward(self, x, targets=None):
         return self.backbone(x)
 
-    __call__ = forward
-
-    def extract_local_descriptors(self, x):
-        return self.backbone.extract_local_descriptors(x)
+    def __call__(self, x, targets=None):
+        return self.forward(x, targets)
 
     def extract_features(self, x):
         return self.backbone.extract_features(x)
@@ -273,8 +121,148 @@ class _HOWWrapper(_Extractor):
     def extract_descriptor(self, x):
         return self.backbone.extract_descriptor(x)
 
+    @torch.no_grad()
     def extract_global_descriptor(self, x):
         return self.backbone.extract_descriptor(x)
+
+
+class GeMPooling:
+    """GeM with a tensor-valued p (models/gem_pooling.py:12-23).  The
+    reference stores p as a 1-element Parameter; the exponent 1/p is formed
+    in fp32 from it, which is what gem_pool's powf path does."""
+
+    def __init__(self, p=3.0, eps=1e-6):
+        self.p = torch.ones(1) * p
+        self.eps = eps
+
+    def __call__(self, x_nhwc):
+        return ops.gem_pool(x_nhwc, float(self.p.item()), self.eps)
+
+
+class GeMModel(_TrunkHeadModel):
+    """resnet trunk -> GeMPooling -> feature_proj Linear(2048, feature_dim)
+    (models/gem_pooling.py:26-92); extract_descriptor adds F.normalize(p=2, dim=1)."""
+
+    def __init__(self, backbone="resnet50", pretrained=False, num_classes=1000, feature_dim=2048, gem_p=3.0,
+                 state_dict=None, seed=0, device="cuda", conv_math="h2", stride_on="3x3"):
+        self._check_backbone(pretrained, backbone, "models/gem_pooling.py:35")
+        backbone_dim = 2048
+        pw, pb = _from_sd(state_dict, "feature_proj") or W.synthetic_linear(feature_dim, backbone_dim, seed + 2)
+        cw, cb = _from_sd(state_dict, "classifier") or W.synthetic_linear(num_classes, feature_dim, seed + 3)
+        head = {k: v.float().contiguous() for k, v in (("proj_w", pw), ("proj_b", pb), ("cls_w", cw), ("cls_b", cb))}
+        self._build(head, None, backbone, state_dict, seed, device, conv_math, stride_on)
+        self.proj_w, self.proj_b, self.cls_w, self.cls_b = (self.w[k] for k in ("proj_w", "proj_b", "cls_w", "cls_b"))
+        self.gem_pool = GeMPooling(p=gem_p)
+        self.feature_dim = feature_dim
+        self.outputdim = feature_dim
+
+    def head(self, x4, x4_amax=None):
+        return ops.linear(self.gem_pool(x4), self.proj_w, self.proj_b)
+
+
+def _from_sd(sd, name):
+    if sd is None:
+        return None
+    for pre in ("", "backbone.", "module.backbone."):
+        k = f"{pre}{name}.weight"
+        if k in sd:
+            return sd[k], sd[f"{pre}{name}.bias"]
+    return None
+
+
+class GeMWrapper(_Wrapper):
+    """models/gem_pooling.py:95-119: training-loop facade over GeMModel."""
+
+    def __init__(self, num_classes, backbone="resnet50", feature_dim=2048, gem_p=3.0, **kw):
+        super().__init__(GeMModel(backbone=backbone, num_classes=num_classes, feature_dim=feature_dim, gem_p=gem_p,
+                                  **kw))
+
+
+def get_gem_model(num_classes, backbone="resnet50", **kwargs):
+    return GeMWrapper(num_classes=num_classes, backbone=backbone, **kwargs)
+
+
+class HOWModel(_TrunkHeadModel):
+    """models/how_vlad.py:107-199, eval mode: resnet trunk -> local_proj (1x1
+    conv 2048 -> local_dim, +bias) -> F.normalize per position -> VLADPooling
+    (alpha = 100) or ASMKPooling -> final_proj Linear(K D or K, 2048);
+    extract_descriptor adds F.normalize.
+
+    Launches after the trunk: the 1x1 conv (conv_math "h2": the f16x2 core on
+    the trunk's max-|x| record; "f32": rr_conv2d), rr_how_vlad or rr_how_asmk on
+    its RAW rows (the per-position normalisation, the distances, the assignment
+    and the aggregation in one read), rr_l2_normalize over the pooled vector
+    (:56, :102), rr_linear, rr_l2_normalize.
+
+    Constructor: the reference's (backbone, pretrained, num_classes, local_dim,
+    pooling_type, num_clusters), then state_dict (trunk keys as networks.ResNet
+    accepts, the reference's index-named nn.Sequential keys included; head
+    keys as weights.how_head_from_state_dict), seed (synthetic weights when
+    state_dict is None), device, conv_math and stride_on as GeMModel."""
+
+    alpha = 100.0  # VLADPooling's default (:17); HOWModel never passes another
+
+    def __init__(self, backbone="resnet50", pretrained=False, num_classes=1000, local_dim=128, pooling_type="vlad",
+                 num_clusters=64, state_dict=None, seed=0, device="cuda", conv_math="h2", stride_on="3x3"):
+        self._check_backbone(pretrained, backbone, "models/how_vlad.py:110")
+        if pooling_type not in ("vlad", "asmk"):
+            raise ValueError(f"Unsupported pooling type: {pooling_type}")
+        if local_dim % 32 or not 32 <= local_dim <= 256 or not 1 <= num_clusters <= 128:
+            raise ValueError("HOWModel: local_dim % 32 == 0, 32 <= local_dim <= 256, 1 <= num_clusters <= 128 "
+                             "(rr_how_vlad / rr_how_asmk)")
+        head = self._load_head(state_dict, seed, W.how_head_from_state_dict, W.synthetic_how_head, pooling_type,
+                               local_dim, num_clusters, num_classes)
+        if ("weights" in head) != (pooling_type == "asmk"):
+            raise ValueError(f"HOWModel: the state dict's head is not a {pooling_type} head")
+        if tuple(head["centroids"].shape) != (num_clusters, local_dim) or head["final_w"].shape[0] != 2048:
+            raise ValueError("HOWModel: head weight shapes do not fit local_dim and num_clusters")
+        self.pooling_type = pooling_type
+        self._build(head, ("local_w", "local_proj"), backbone, state_dict, seed, device, conv_math, stride_on)
+        self.local_proj = HeadConv(self.w["local_w"].view(local_dim, 1, 1, -1), conv_math)
+        self.local_dim, self.num_clusters = local_dim, num_clusters
+        self.outputdim = 2048
+
+    def local_map(self, x4, x4_amax=None):
+        """The raw local_proj output [B,H,W,local_dim] of a trunk map x4 NHWC."""
+        if self.conv_math == "h2" and x4_amax is None:
+            x4_amax = ops.amax_of(x4)
+        return self.local_proj(x4, x4_amax, self.w["local_b"])
+
+    def head(self, x4, x4_amax=None, taps=None):
+        """x4 NHWC -> features [B,2048] (:155-175).  taps: a dict that receives
+        local (the raw local_proj rows [B,N,D]), pooled (after its L2) and
+        features (tests)."""
+        y = self.local_map(x4, x4_amax)
+        if self.pooling_type == "vlad":
+            v = ops.how_vlad(y, self.w["centroids"], self.alpha)
+        else:
+            v = ops.how_asmk(y, self.w["centroids"], self.w["weights"])
+        v = ops.l2_normalize(v, EPS_L2, out=v)
+        f = ops.linear(v, self.w["final_w"], self.w["final_b"])
+        if taps is not None:
+            taps.update(local=y.view(y.shape[0], -1, y.shape[-1]), pooled=v, features=f)
+        return f
+
+    @torch.no_grad()
+    def extract_local_descriptors(self, x):
+        """L2-normalised local descriptors [B,N,D] (:149-164), for callers: the
+        pooling kernels normalise on load and never write these."""
+        y = self.local_map(*self.trunk_map(self._input(x)))
+        b, d = y.shape[0], y.shape[-1]
+        return ops.l2_normalize(y.view(-1, d), EPS_L2).view(b, -1, d)
+
+
+class _HOWWrapper(_Wrapper):
+    """models/how_vlad.py:202-255: training-loop facade over HOWModel."""
+
+    pooling_type = None
+
+    def __init__(self, num_classes, backbone="resnet50", local_dim=128, num_clusters=64, **kw):
+        super().__init__(HOWModel(backbone=backbone, num_classes=num_classes, local_dim=local_dim,
+                                  pooling_type=self.pooling_type, num_clusters=num_clusters, **kw))
+
+    def extract_local_descriptors(self, x):
+        return self.backbone.extract_local_descriptors(x)
 
 
 class HOWVLADWrapper(_HOWWrapper):
@@ -293,7 +281,7 @@ def get_how_asmk_model(num_classes, backbone="resnet50", **kwargs):
     return HOWASMKWrapper(num_classes=num_classes, backbone=backbone, **kwargs)
 
 
-class SoSNetModel(_Extractor):
+class SoSNetModel(_TrunkHeadModel):
     """models/sosnet.py:95-183, eval mode: resnet trunk -> SimilarityAttention
     (a per-position MLP 2048 -> 512 -> 256 -> 1, sigmoid, multiply) ->
     SecondOrderPooling (1x1 conv 2048 -> second_order_dim, centred covariance
@@ -323,24 +311,15 @@ class SoSNetModel(_Extractor):
     the names stay in OUT_OF_SCOPE and out of MODEL_REGISTRY (build the model
     with get_sosnet_model)."""
 
-    in_channels = 4
-
     def __init__(self, backbone="resnet50", pretrained=False, num_classes=1000, feature_dim=2048, second_order_dim=512,
                  use_attention=True, state_dict=None, seed=0, device="cuda", conv_math="h2", stride_on="3x3"):
-        if pretrained:
-            raise ValueError("pretrained weights need a download; pass a local state_dict instead "
-                             "(models/sosnet.py:98 defaults to pretrained=True)")
-        if backbone not in ("resnet50", "resnet101"):
-            raise ValueError(f"Unsupported backbone: {backbone}")
+        self._check_backbone(pretrained, backbone, "models/sosnet.py:98")
         c = second_order_dim
         if c % 32 or not 32 <= c <= 512:
             raise ValueError("SoSNetModel: second_order_dim % 32 == 0, 32 <= second_order_dim <= 512 (rr_sos_cov; at "
                              "2048 the reference drops the projection and its first Linear would hold 17 GB)")
-        if state_dict is None:
-            head = W.sos_head_from_state_dict(W.synthetic_sos_head(seed + 1, c, num_classes, use_attention,
-                                                                   feature_dim))
-        else:
-            head = W.sos_head_from_state_dict(state_dict)
+        head = self._load_head(state_dict, seed, W.sos_head_from_state_dict, W.synthetic_sos_head, c, num_classes,
+                               use_attention, feature_dim)
         if ("att_w1" in head) != bool(use_attention):
             raise ValueError("SoSNetModel: use_attention does not fit the state dict's head")
         if head["proj_w"].shape[0] != c or head["fp0_w"].shape[0] != feature_dim:
@@ -348,26 +327,15 @@ class SoSNetModel(_Extractor):
         if use_attention and (head["att_w1"].shape[0] % 32 or head["att_w2"].shape[0] % 4 or
                               not 4 <= head["att_w2"].shape[0] <= 512):
             raise ValueError("SoSNetModel: the attention MLP's widths do not fit rr_sos_cov")
-        self.device = torch.device(device)
-        self.conv_math = conv_math
         self.use_attention = bool(use_attention)
         self.att_b3 = float(head.pop("att_b3")[0]) if use_attention else 0.0  # read on the host, before any device work
-        self.backbone = ResNet(backbone, state_dict, seed, device, conv_math=conv_math, stride_on=stride_on)
-        if head["proj_w"].shape[1] != self.backbone.outputdim_block5:
-            raise ValueError("SoSNetModel: second_order_pool.proj does not fit the trunk")
-        self.w = {k: v.to(self.device) for k, v in head.items()}
-        self.proj_w = self.w["proj_w"].view(c, 1, 1, -1)
-        self.proj_h2 = ops.H2Conv(self.proj_w) if conv_math == "h2" else None
+        self._build(head, ("proj_w", "second_order_pool.proj"), backbone, state_dict, seed, device, conv_math,
+                    stride_on)
+        self.proj = HeadConv(self.w["proj_w"].view(c, 1, 1, -1), conv_math)
         if use_attention:
-            self.att_w1 = self.w["att_w1"].view(self.w["att_w1"].shape[0], 1, 1, -1)
-            self.att_h2 = ops.H2Conv(self.att_w1) if conv_math == "h2" else None
+            self.att1 = HeadConv(self.w["att_w1"].view(self.w["att_w1"].shape[0], 1, 1, -1), conv_math)
         self.second_order_dim, self.feature_dim = c, feature_dim
         self.outputdim = feature_dim
-
-    def _conv(self, x4, x4_amax, w, wc, bias, relu):
-        if self.conv_math == "h2":
-            return ops.conv2d_h2(x4, x4_amax, wc, bias, 1, 0, None, relu)
-        return ops.conv2d(x4, w, bias, 1, 0, None, relu)
 
     def head(self, x4, x4_amax=None, taps=None):
         """x4 NHWC -> features [B,feature_dim] (:144-161).  taps: a dict that
@@ -379,12 +347,12 @@ class SoSNetModel(_Extractor):
             raise ValueError("SoSNetModel: a map with one position has no covariance (the reference divides by "
                              "N - 1 = 0 and returns NaN, models/sosnet.py:45)")
         if self.conv_math == "h2" and x4_amax is None:
-            x4_amax = ops.amax_f32(x4, ops.amax_records(1, x4.device)[0])
+            x4_amax = ops.amax_of(x4)
         hid = None
         if self.use_attention:
-            h1 = self._conv(x4, x4_amax, self.att_w1, self.att_h2, self.w["att_b1"], True)
+            h1 = self.att1(x4, x4_amax, self.w["att_b1"], relu=True)
             hid = ops.linear_ex(h1.view(b * n, -1), self.w["att_w2"], self.w["att_b2"], act=1).view(b, n, -1)
-        z = self._conv(x4, x4_amax, self.proj_w, self.proj_h2, None, False).view(b, n, -1)
+        z = self.proj(x4, x4_amax, None).view(b, n, -1)
         got = ops.sos_cov(z, hid, self.w.get("att_w3"), self.att_b3, want_att=taps is not None)
         hidden = ops.linear_splitk(got[0], self.w["fp0_w"], self.w["fp0_b"], row_scale=got[1], act=1)
         f = ops.linear(hidden, self.w["fp3_w"], self.w["fp3_b"])
@@ -392,69 +360,21 @@ class SoSNetModel(_Extractor):
             taps.update(att=got[2], cov=got[0], inv_norm=got[1], hidden=hidden, features=f)
         return f
 
-    def _trunk(self, x_nhwc, hook=None):
-        if self.conv_math == "h2":
-            return self.backbone(x_nhwc, hook=hook, return_amax=True)
-        return self.backbone(x_nhwc), None
 
-    def extract_features_nhwc(self, x_nhwc, hook=None):
-        return self.head(*self._trunk(x_nhwc, hook))
-
-    @torch.no_grad()
-    def extract_features(self, x):
-        return self.extract_features_nhwc(self._input(x))
-
-    def forward_test_nhwc(self, x_nhwc, hook=None):
-        f = self.extract_features_nhwc(x_nhwc, hook)
-        return ops.l2_normalize(f, EPS_L2, out=f)
-
-    @torch.no_grad()
-    def extract_descriptor(self, x):
-        return self.forward_test(x)
-
-    @torch.no_grad()
-    def forward(self, x, targets=None):
-        feats = self.extract_features(x)
-        return None, ops.linear(feats, self.w["cls_w"], self.w["cls_b"])
-
-    __call__ = forward
-
-
-class SoSNetWrapper(_Extractor):
+class SoSNetWrapper(_Wrapper):
     """models/sosnet.py:186-212: training-loop facade over SoSNetModel."""
-
-    in_channels = 4
 
     def __init__(self, num_classes, backbone="resnet50", feature_dim=2048, second_order_dim=512, use_attention=True,
                  **kw):
-        self.backbone = SoSNetModel(backbone=backbone, num_classes=num_classes, feature_dim=feature_dim,
-                                    second_order_dim=second_order_dim, use_attention=use_attention, **kw)
-        self.outputdim = self.backbone.outputdim
-
-    def forward_test_nhwc(self, x_nhwc, hook=None):
-        return self.backbone.forward_test_nhwc(x_nhwc, hook)
-
-    @torch.no_grad()
-    def forward(self, x, targets=None):
-        return self.backbone(x)
-
-    __call__ = forward
-
-    def extract_features(self, x):
-        return self.backbone.extract_features(x)
-
-    def extract_descriptor(self, x):
-        return self.backbone.extract_descriptor(x)
-
-    def extract_global_descriptor(self, x):
-        return self.backbone.extract_descriptor(x)
+        super().__init__(SoSNetModel(backbone=backbone, num_classes=num_classes, feature_dim=feature_dim,
+                                     second_order_dim=second_order_dim, use_attention=use_attention, **kw))
 
 
 def get_sosnet_model(num_classes, backbone="resnet50", **kwargs):
     return SoSNetWrapper(num_classes=num_classes, backbone=backbone, **kwargs)
 
 
-class SpoCModel(_Extractor):
+class SpoCModel(_TrunkHeadModel):
     """models/spoc.py:97-195, eval mode: resnet trunk -> ContextualAttention
     (:52-94: two 3x3 convs with BN and ReLU to context_dim channels, a 1x1
     attention conv with a sigmoid, and a 1x1 refine conv over cat[x a, ctx])
@@ -489,50 +409,31 @@ class SpoCModel(_Extractor):
     names stay in OUT_OF_SCOPE and out of MODEL_REGISTRY (build the model with
     get_spoc_model)."""
 
-    in_channels = 4
-
     def __init__(self, backbone="resnet50", pretrained=False, num_classes=1000, feature_dim=2048,
                  pyramid_levels=(1, 2, 4), context_dim=512, use_context=True, state_dict=None, seed=0, device="cuda",
                  conv_math="h2", stride_on="3x3"):
-        if pretrained:
-            raise ValueError("pretrained weights need a download; pass a local state_dict instead "
-                             "(models/spoc.py:100 defaults to pretrained=True)")
-        if backbone not in ("resnet50", "resnet101"):
-            raise ValueError(f"Unsupported backbone: {backbone}")
+        self._check_backbone(pretrained, backbone, "models/spoc.py:100")
         dc = context_dim
         if dc % 32 or not 32 <= dc <= 2048:
             raise ValueError("SpoCModel: context_dim % 32 == 0, 32 <= context_dim <= 2048 (rr_spoc_refine)")
         levels = [int(v) for v in pyramid_levels]
         if not 1 <= len(levels) <= 8 or min(levels) < 1:
             raise ValueError("SpoCModel: pyramid_levels must hold 1 to 8 levels, each >= 1 (rr_spp_max)")
-        if state_dict is None:
-            head = W.spoc_head_from_state_dict(W.synthetic_spoc_head(seed + 1, dc, num_classes, use_context,
-                                                                     feature_dim))
-        else:
-            head = W.spoc_head_from_state_dict(state_dict)
+        head = self._load_head(state_dict, seed, W.spoc_head_from_state_dict, W.synthetic_spoc_head, dc, num_classes,
+                               use_context, feature_dim)
         if ("ce0_w" in head) != bool(use_context):
             raise ValueError("SpoCModel: use_context does not fit the state dict's head")
         if head["agg_w"].shape[0] != feature_dim or (use_context and head["ce0_w"].shape[0] != dc):
             raise ValueError("SpoCModel: head weight shapes do not fit feature_dim and context_dim")
-        self.device = torch.device(device)
-        self.conv_math = conv_math
         self.use_context = bool(use_context)
         self.pyramid_levels = levels
         self.att_b = head.pop("att_b") if use_context else 0.0  # a python float, read before any device work
-        self.backbone = ResNet(backbone, state_dict, seed, device, conv_math=conv_math, stride_on=stride_on)
-        if head["agg_w"].shape[1] != self.backbone.outputdim_block5:
-            raise ValueError("SpoCModel: feature_aggregation does not fit the trunk")
-        self.w = {k: v.to(self.device) for k, v in head.items()}
-        self.h2 = {}
-        if use_context and conv_math == "h2":
-            self.h2 = {k: ops.H2Conv(self.w[k]) for k in ("ce0_w", "ce1_w", "refine_wx")}
+        self._build(head, ("agg_w", "feature_aggregation"), backbone, state_dict, seed, device, conv_math, stride_on)
+        self.convs = {}
+        if use_context:
+            self.convs = {k: HeadConv(self.w[k], conv_math) for k in ("ce0_w", "ce1_w", "refine_wx")}
         self.context_dim, self.feature_dim = dc, feature_dim
         self.outputdim = feature_dim
-
-    def _conv(self, x, x_amax, key, bias, pad, relu, y_amax=None):
-        if self.conv_math == "h2":
-            return ops.conv2d_h2(x, x_amax, self.h2[key], bias, 1, pad, None, relu, y_amax)
-        return ops.conv2d(x, self.w[key], bias, 1, pad, None, relu)
 
     def head(self, x4, x4_amax=None, taps=None):
         """x4 NHWC -> features [B,feature_dim] (:152-173).  taps: a dict that
@@ -552,11 +453,11 @@ class SpoCModel(_Extractor):
             c1_amax = None
             if self.conv_math == "h2":
                 if x4_amax is None:
-                    x4_amax = ops.amax_f32(x4, ops.amax_records(1, x4.device)[0])
+                    x4_amax = ops.amax_of(x4)
                 c1_amax = ops.amax_records(1, x4.device)[0]
-            c1 = self._conv(x4, x4_amax, "ce0_w", self.w["ce0_b"], 1, True, c1_amax)
-            ctx = self._conv(c1, c1_amax, "ce1_w", self.w["ce1_b"], 1, True)
-            u = self._conv(x4, x4_amax, "refine_wx", None, 0, False)
+            c1 = self.convs["ce0_w"](x4, x4_amax, self.w["ce0_b"], pad=1, relu=True, y_amax=c1_amax)
+            ctx = self.convs["ce1_w"](c1, c1_amax, self.w["ce1_b"], pad=1, relu=True)
+            u = self.convs["refine_wx"](x4, x4_amax, None)
             got = ops.spoc_refine(u, ctx, self.w["att_w"], self.att_b, self.w["refine_wc"], self.w["refine_b"],
                                   want_att=taps is not None, out=u)
             refined, att = got if taps is not None else (got, None)
@@ -569,70 +470,22 @@ class SpoCModel(_Extractor):
                         hidden=hidden, features=f)
         return f
 
-    def _trunk(self, x_nhwc, hook=None):
-        if self.conv_math == "h2":
-            return self.backbone(x_nhwc, hook=hook, return_amax=True)
-        return self.backbone(x_nhwc), None
 
-    def extract_features_nhwc(self, x_nhwc, hook=None):
-        return self.head(*self._trunk(x_nhwc, hook))
-
-    @torch.no_grad()
-    def extract_features(self, x):
-        return self.extract_features_nhwc(self._input(x))
-
-    def forward_test_nhwc(self, x_nhwc, hook=None):
-        f = self.extract_features_nhwc(x_nhwc, hook)
-        return ops.l2_normalize(f, EPS_L2, out=f)
-
-    @torch.no_grad()
-    def extract_descriptor(self, x):
-        return self.forward_test(x)
-
-    @torch.no_grad()
-    def forward(self, x, targets=None):
-        feats = self.extract_features(x)
-        return None, ops.linear(feats, self.w["cls_w"], self.w["cls_b"])
-
-    __call__ = forward
-
-
-class SpoCWrapper(_Extractor):
+class SpoCWrapper(_Wrapper):
     """models/spoc.py:198-225: training-loop facade over SpoCModel."""
-
-    in_channels = 4
 
     def __init__(self, num_classes, backbone="resnet50", feature_dim=2048, pyramid_levels=(1, 2, 4), context_dim=512,
                  use_context=True, **kw):
-        self.backbone = SpoCModel(backbone=backbone, num_classes=num_classes, feature_dim=feature_dim,
-                                  pyramid_levels=pyramid_levels, context_dim=context_dim, use_context=use_context,
-                                  **kw)
-        self.outputdim = self.backbone.outputdim
-
-    def forward_test_nhwc(self, x_nhwc, hook=None):
-        return self.backbone.forward_test_nhwc(x_nhwc, hook)
-
-    @torch.no_grad()
-    def forward(self, x, targets=None):
-        return self.backbone(x)
-
-    __call__ = forward
-
-    def extract_features(self, x):
-        return self.backbone.extract_features(x)
-
-    def extract_descriptor(self, x):
-        return self.backbone.extract_descriptor(x)
-
-    def extract_global_descriptor(self, x):
-        return self.backbone.extract_descriptor(x)
+        super().__init__(SpoCModel(backbone=backbone, num_classes=num_classes, feature_dim=feature_dim,
+                                   pyramid_levels=pyramid_levels, context_dim=context_dim, use_context=use_context,
+                                   **kw))
 
 
 def get_spoc_model(num_classes, backbone="resnet50", **kwargs):
     return SpoCWrapper(num_classes=num_classes, backbone=backbone, **kwargs)
 
 
-class TokenModel(_Extractor):
+class TokenModel(_TrunkHeadModel):
     """models/token_based.py:89-159, eval mode: resnet trunk -> TokenAggregator
     (:35-86: input_proj Linear(2048, hidden_dim) per position, + the sinusoidal
     pe[i], the learnable global token in front, a post-norm nn.TransformerEncoder
@@ -674,15 +527,9 @@ class TokenModel(_Extractor):
     the names stay in OUT_OF_SCOPE and out of MODEL_REGISTRY (build the model
     with get_token_model)."""
 
-    in_channels = 4
-
     def __init__(self, backbone="resnet50", pretrained=False, num_classes=1000, feature_dim=2048, hidden_dim=512,
                  num_heads=8, num_layers=2, state_dict=None, seed=0, device="cuda", conv_math="h2", stride_on="3x3"):
-        if pretrained:
-            raise ValueError("pretrained weights need a download; pass a local state_dict instead "
-                             "(models/token_based.py:92 defaults to pretrained=True)")
-        if backbone not in ("resnet50", "resnet101"):
-            raise ValueError(f"Unsupported backbone: {backbone}")
+        self._check_backbone(pretrained, backbone, "models/token_based.py:92")
         d, nh = hidden_dim, num_heads
         if d % 64 or not 64 <= d <= 1024:
             raise ValueError("TokenModel: hidden_dim % 64 == 0, 64 <= hidden_dim <= 1024 (rr_cls_attn_pool)")
@@ -692,27 +539,19 @@ class TokenModel(_Extractor):
             raise ValueError("TokenModel: num_layers >= 1")
         if num_layers > 1 and d != 64 * nh:
             raise ValueError("TokenModel: hidden_dim == 64 num_heads when num_layers > 1 (rr_attention's head width)")
-        if state_dict is None:
-            head = W.tokagg_head_from_state_dict(W.synthetic_tokagg_head(seed + 1, d, nh, num_layers, num_classes,
-                                                                         feature_dim))
-        else:
-            head = W.tokagg_head_from_state_dict(state_dict)
+        head = self._load_head(state_dict, seed, W.tokagg_head_from_state_dict, W.synthetic_tokagg_head, d, nh,
+                               num_layers, num_classes, feature_dim)
         if head["in_w"].shape[0] != d or W.tokagg_num_layers(head) != num_layers or \
                 head["fp_w"].shape[0] != feature_dim:
             raise ValueError("TokenModel: head weight shapes do not fit hidden_dim, num_layers and feature_dim")
         a, a0, m, m0 = W.tokagg_fold_last_layer(W.tokagg_layer(head, num_layers - 1), nh)
         pos = torch.cat([torch.zeros(1, d), head.pop("pe")]).contiguous()  # row 0: the global token gets no term
         self.max_len = pos.shape[0] - 1
-        self.device = torch.device(device)
-        self.conv_math = conv_math
-        self.backbone = ResNet(backbone, state_dict, seed, device, conv_math=conv_math, stride_on=stride_on)
-        if head["in_w"].shape[1] != self.backbone.outputdim_block5:
-            raise ValueError("TokenModel: token_aggregator.input_proj does not fit the trunk")
-        self.w = {k: v.to(self.device) for k, v in head.items()}
+        self._build(head, ("in_w", "token_aggregator.input_proj"), backbone, state_dict, seed, device, conv_math,
+                    stride_on)
         self.w.update(pos=pos.to(self.device), fold_a=a.to(self.device), fold_a0=a0.to(self.device),
                       fold_m=m.to(self.device), fold_m0=m0.to(self.device))
-        self.in_w = self.w["in_w"].view(d, 1, 1, -1)
-        self.in_h2 = ops.H2Conv(self.in_w) if conv_math == "h2" else None
+        self.input_proj = HeadConv(self.w["in_w"].view(d, 1, 1, -1), conv_math)
         self.hidden_dim, self.num_heads, self.num_layers, self.feature_dim = d, nh, num_layers, feature_dim
         self.outputdim = feature_dim
 
@@ -759,12 +598,9 @@ class TokenModel(_Extractor):
             raise ValueError(f"TokenModel: {n} positions exceed the positional encoding's max_len = {self.max_len} "
                              "(models/token_based.py:16, :32: the reference's broadcast raises; inputs up to 448 x 448)")
         seq = 1 + n
-        if self.conv_math == "h2":
-            if x4_amax is None:
-                x4_amax = ops.amax_f32(x4, ops.amax_records(1, x4.device)[0])
-            y = ops.conv2d_h2(x4, x4_amax, self.in_h2, self.w["in_b"], 1, 0, None, False)
-        else:
-            y = ops.conv2d(x4, self.in_w, self.w["in_b"], 1, 0, None, False)
+        if self.conv_math == "h2" and x4_amax is None:
+            x4_amax = ops.amax_of(x4)
+        y = self.input_proj(x4, x4_amax, self.w["in_b"])
         x = ops.vit_tokens(y.view(b * n, d), b, self.w["global_token"], self.w["pos"])
         if taps is not None:
             taps["tokens"] = x.view(b, seq, d)
@@ -782,62 +618,14 @@ class TokenModel(_Extractor):
             taps.update(agg=agg, features=f)
         return f
 
-    def _trunk(self, x_nhwc, hook=None):
-        if self.conv_math == "h2":
-            return self.backbone(x_nhwc, hook=hook, return_amax=True)
-        return self.backbone(x_nhwc), None
 
-    def extract_features_nhwc(self, x_nhwc, hook=None):
-        return self.head(*self._trunk(x_nhwc, hook))
-
-    @torch.no_grad()
-    def extract_features(self, x):
-        return self.extract_features_nhwc(self._input(x))
-
-    def forward_test_nhwc(self, x_nhwc, hook=None):
-        f = self.extract_features_nhwc(x_nhwc, hook)
-        return ops.l2_normalize(f, EPS_L2, out=f)
-
-    @torch.no_grad()
-    def extract_descriptor(self, x):
-        return self.forward_test(x)
-
-    @torch.no_grad()
-    def forward(self, x, targets=None):
-        feats = self.extract_features(x)
-        return None, ops.linear(feats, self.w["cls_w"], self.w["cls_b"])
-
-    __call__ = forward
-
-
-class TokenWrapper(_Extractor):
+class TokenWrapper(_Wrapper):
     """models/token_based.py:162-189: training-loop facade over TokenModel."""
-
-    in_channels = 4
 
     def __init__(self, num_classes, backbone="resnet50", feature_dim=2048, hidden_dim=512, num_heads=8, num_layers=2,
                  **kw):
-        self.backbone = TokenModel(backbone=backbone, num_classes=num_classes, feature_dim=feature_dim,
-                                   hidden_dim=hidden_dim, num_heads=num_heads, num_layers=num_layers, **kw)
-        self.outputdim = self.backbone.outputdim
-
-    def forward_test_nhwc(self, x_nhwc, hook=None):
-        return self.backbone.forward_test_nhwc(x_nhwc, hook)
-
-    @torch.no_grad()
-    def forward(self, x, targets=None):
-        return self.backbone(x)
-
-    __call__ = forward
-
-    def extract_features(self, x):
-        return self.backbone.extract_features(x)
-
-    def extract_descriptor(self, x):
-        return self.backbone.extract_descriptor(x)
-
-    def extract_global_descriptor(self, x):
-        return self.backbone.extract_descriptor(x)
+        super().__init__(TokenModel(backbone=backbone, num_classes=num_classes, feature_dim=feature_dim,
+                                    hidden_dim=hidden_dim, num_heads=num_heads, num_layers=num_layers, **kw))
 
 
 def get_token_model(num_classes, backbone="resnet50", **kwargs):

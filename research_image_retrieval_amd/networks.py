@@ -16,6 +16,11 @@ from . import weights as W
 EPS_L2 = 1e-12  # F.normalize default eps (networks/RetrievalNet.py:343)
 
 
+def _check_conv_math(conv_math):
+    if conv_math not in ("h2", "f32"):
+        raise ValueError("conv_math must be 'h2' or 'f32'")
+
+
 class ResNet:
     """torchvision resnet children[:-2] trunk (networks/backbone.py:60-109:
     block1 = conv1/bn1/relu/maxpool, block2..5 = layer1..4), NHWC, BN folded.
@@ -40,8 +45,7 @@ class ResNet:
     outputdim_block4 = 1024
 
     def __init__(self, name="resnet101", state_dict=None, seed=0, device="cuda", conv_math="h2", stride_on="3x3"):
-        if conv_math not in ("h2", "f32"):
-            raise ValueError("conv_math must be 'h2' or 'f32'")
+        _check_conv_math(conv_math)
         W.block_strides(1, stride_on)  # validates
         self.stride_on = stride_on
         if name not in W.RESNET_LAYERS:
@@ -85,8 +89,8 @@ class ResNet:
             plans[key] = ops.TrunkPlan(self, lag)
         return plans[key]
 
-    def _forward_h2(self, x, return_x3, hook=None, return_x3_amax=False, return_amax=False):
-        """The trunk on the f16x2 core: every conv reads its input's max-|x|
+    def _forward_h2(self, x, hook, want_x3):
+        """maps() on the f16x2 core: every conv reads its input's max-|x|
         record and writes its output's (one zeroed [2 + 3 blocks, 64] tensor per
         forward); the max-pool output reuses the stem's record (every stem
         output lies in some 3x3/2 window, so the max is the same); the stem,
@@ -95,12 +99,9 @@ class ResNet:
         first block runs conv3 and its downsample projection as one GEMM
         (ops.bottleneck_out_h2), so the projected identity never reaches HBM.
         hook(i), if given, is called after the i-th conv launch (i = 0: the
-        stem) -- the point where a caller can record a stream event.
-        return_x3_amax (with return_x3): also return x3's max-|x| record, which
-        its conv3 published, for a caller that runs another f16x2 conv on x3:
-        (x3, x4, record).  return_amax: the output's own record is appended
-        to whatever is returned, (..., x4's record), for a caller that runs
-        another f16x2 conv on x4."""
+        stem) -- the point where a caller can record a stream event.  The
+        records returned are the ones x3's and x4's conv3 published, for a
+        caller that runs another f16x2 conv on either map."""
         cv, h2 = self.convs, self.convs_h2
         hook = hook or (lambda i: None)
         rec = ops.amax_records(2 + 3 * sum(self.layers), x.device)
@@ -133,28 +134,21 @@ class ResNet:
                 xa, r = rec[r + 2], r + 3
             if li == 2:
                 x3, x3a = x, xa
-        if return_x3 and return_x3_amax:
-            ret = (x3, x, x3a)
-        else:
-            ret = (x3, x) if return_x3 else (x,)
-        if return_amax:
-            return ret + (xa,)
-        return ret if return_x3 else x
+        return (x3, x, x3a, xa) if want_x3 else (None, x, None, xa)
 
-    def forward(self, x, return_x3=False, hook=None, return_x3_amax=False, return_amax=False):
-        """x: NHWC fp32 with 3 channels or 4 (zero 4th channel, preferred).
-        return_x3: also return layer3's output, as ResNet_DOLG.forward's
-        (x3, x4) (networks/backbone.py:236-242).  return_x3_amax (f16x2 trunk,
-        with return_x3): (x3, x4, x3's max-|x| record).  return_amax (f16x2
-        trunk): x4's max-|x| record comes last, (x4, record) or (x3, x4, [x3's
-        record,] record)."""
+    def maps(self, x, hook=None, want_x3=False):
+        """x: NHWC fp32 with 3 channels or 4 (zero 4th channel, preferred) ->
+        (x3, x4, x3_amax, x4_amax), the order _Extractor._tail and
+        ops.TrunkPlan.forward_u8(return_x3=True) use: layer3's and layer4's
+        outputs (ResNet_DOLG.forward's (x3, x4), networks/backbone.py:236-242)
+        and their max-|x| records.  The records are None on the "f32" trunk;
+        x3 and its record are None unless want_x3, so a caller that never reads
+        x3 does not keep it alive.  hook: see _forward_h2 (the "f32" trunk
+        never calls it)."""
         if x.shape[-1] == 3:
             x = torch.nn.functional.pad(x, (0, 1))
         if self.conv_math == "h2":
-            return self._forward_h2(x.contiguous(), return_x3, hook, return_x3_amax, return_amax)
-        if return_x3_amax or return_amax:
-            raise ValueError("return_x3_amax / return_amax: only the f16x2 trunk (conv_math='h2') keeps max-|x| "
-                             "records")
+            return self._forward_h2(x.contiguous(), hook, want_x3)
         x = self._conv(x, "conv1", 2, 3, True)
         x = ops.maxpool2d(x, 3, 2, 1)
         x3 = None
@@ -168,7 +162,23 @@ class ResNet:
                 x = self._conv(y, f"{p}.conv3", 1, 0, True, residual=idn)
             if li == 2:
                 x3 = x
-        return (x3, x) if return_x3 else x
+        return (x3 if want_x3 else None), x, None, None
+
+    def forward(self, x, return_x3=False, hook=None, return_x3_amax=False, return_amax=False):
+        """A selection from maps(x, hook, return_x3): x4; with return_x3 (x3,
+        x4); return_x3_amax (f16x2 trunk, with return_x3) appends x3's max-|x|
+        record; return_amax (f16x2 trunk) appends x4's, last: (x4, record) or
+        (x3, x4, [x3's record,] record)."""
+        if (return_x3_amax or return_amax) and self.conv_math != "h2":
+            raise ValueError("return_x3_amax / return_amax: only the f16x2 trunk (conv_math='h2') keeps max-|x| "
+                             "records")
+        x3, x4, x3a, x4a = self.maps(x, hook, return_x3)
+        ret = (x3, x4) if return_x3 else (x4,)
+        if return_x3 and return_x3_amax:
+            ret += (x3a,)
+        if return_amax:
+            ret += (x4a,)
+        return ret if len(ret) > 1 else x4
 
     __call__ = forward
 
@@ -182,6 +192,25 @@ class gem:
 
     def __call__(self, x_nhwc):
         return ops.gem_pool(x_nhwc, self.p, self.eps)
+
+
+class HeadConv:
+    """A head's stride-1 conv on the core its trunk runs on.  w: [Cout,KH,KW,
+    Cin] on the device; conv_math "h2": the f16x2 core (the weights split once
+    here), "f32": rr_conv2d."""
+
+    def __init__(self, w, conv_math):
+        _check_conv_math(conv_math)
+        self.w = w
+        self.h2 = ops.H2Conv(w) if conv_math == "h2" else None
+
+    def __call__(self, x, x_amax, bias, pad=0, relu=False, residual=None, y_amax=None):
+        """x_amax: x's max-|x| record, passed on as given (ops.amax_of for a
+        caller that has none); y_amax (optional, zeroed) gets max |y|.  The
+        "f32" core reads neither."""
+        if self.h2 is not None:
+            return ops.conv2d_h2(x, x_amax, self.h2, bias, 1, pad, residual, relu, y_amax)
+        return ops.conv2d(x, self.w, bias, 1, pad, residual, relu)
 
 
 class _Extractor:
@@ -204,17 +233,11 @@ class _Extractor:
         x = x.float() if x.dtype != torch.float32 else x
         return ops.nchw_to_nhwc(x.contiguous(), out_c=self.in_channels)
 
-    def forward_test_nhwc(self, x_nhwc):
-        raise NotImplementedError
-
-    @torch.no_grad()
-    def forward_test(self, x):
-        return self.forward_test_nhwc(self._input(x))
-
     # A ResNet-based extractor names its trunk and what follows it, so that
-    # forward_test_u8 can run the trunk as the native plan (ResNet.plan):
-    # _trunk() -> the networks.ResNet (None: no such trunk), _needs_x3: the tail
-    # reads layer3's output, _tail(x3, x4, x3_amax, x4_amax) -> descriptors.
+    # forward_test_nhwc can run them in turn and forward_test_u8 can run the
+    # trunk as the native plan (ResNet.plan): _trunk() -> the networks.ResNet
+    # (None: no such trunk), _needs_x3: the tail reads layer3's output,
+    # _tail(x3, x4, x3_amax, x4_amax) -> descriptors.
     _needs_x3 = False
 
     def _trunk(self):
@@ -222,6 +245,17 @@ class _Extractor:
 
     def _tail(self, x3, x4, x3_amax, x4_amax):
         raise NotImplementedError
+
+    def forward_test_nhwc(self, x_nhwc, hook=None):
+        """hook: ResNet._forward_h2's (forward_test_u8_streams records its gate there)."""
+        t = self._trunk()
+        if t is None:
+            raise NotImplementedError
+        return self._tail(*t.maps(x_nhwc, hook, self._needs_x3))
+
+    @torch.no_grad()
+    def forward_test(self, x):
+        return self.forward_test_nhwc(self._input(x))
 
     @torch.no_grad()
     def forward_test_u8(self, img_nhwc_u8):
@@ -323,9 +357,6 @@ class GeM(_Extractor):
         f = ops.linear(f, self.whiten_w, self.whiten_b)
         return ops.l2_normalize(f, EPS_L2, out=f)
 
-    def forward_test_nhwc(self, x_nhwc, hook=None):
-        return self._tail(None, self.backbone(x_nhwc, hook=hook), None, None)
-
 
 class DOLG(_Extractor):
     """DOLG (networks/RetrievalNet.py:367-431, forward_test; local branch
@@ -356,10 +387,7 @@ class DOLG(_Extractor):
         if pretrained is not None:
             raise ValueError("networks.DOLG: pretrained weights cannot be downloaded; pass state_dict")
         self.device = torch.device(device)
-        if state_dict is None:
-            head = W.dolg_head_from_state_dict(W.synthetic_dolg_head(seed + 1))
-        else:
-            head = W.dolg_head_from_state_dict(state_dict)
+        head = W.dolg_head_from_state_dict(W.synthetic_dolg_head(seed + 1) if state_dict is None else state_dict)
         self.globalmodel = ResNet(backbone, state_dict, seed, device, conv_math, stride_on)
         cin = self.globalmodel.outputdim_block4
         if tuple(head["conv1_w"].shape[1:]) != (1, 1, cin) or head["fc_t_w"].shape[1] != ResNet.outputdim_block5 or \
@@ -367,9 +395,8 @@ class DOLG(_Extractor):
             raise ValueError("networks.DOLG: head weight shapes do not fit the trunk")
         self.conv_math = conv_math
         self.pool_g = gem(3.0)
-        self.conv1_w = head["conv1_w"].to(self.device)
+        self.conv1 = HeadConv(head["conv1_w"].to(self.device), conv_math)
         self.conv1_b = head["conv1_b"].to(self.device)
-        self.conv1_h2 = ops.H2Conv(self.conv1_w) if conv_math == "h2" else None
         self.conv2_w = head["conv2_w"].to(self.device)
         self.conv2_b = head["conv2_b"]
         self.fc_t = (head["fc_t_w"].to(self.device), head["fc_t_b"].to(self.device))
@@ -379,18 +406,7 @@ class DOLG(_Extractor):
 
     def local_mean(self, x3, x3_amax=None):
         """m [B,1024]: the spatial mean of SpatialAttention2d's output on x3."""
-        if self.conv_math == "h2":
-            y = ops.conv2d_h2(x3, x3_amax, self.conv1_h2, self.conv1_b, 1, 0, None, False)
-        else:
-            y = ops.conv2d(x3, self.conv1_w, self.conv1_b, 1, 0, None, False)
-        return ops.dolg_local_pool(y, self.conv2_w, self.conv2_b)
-
-    def forward_test_nhwc(self, x_nhwc, hook=None):
-        if self.conv_math == "h2":
-            x3, x4, x3a = self.globalmodel(x_nhwc, return_x3=True, hook=hook, return_x3_amax=True)
-        else:
-            (x3, x4), x3a = self.globalmodel(x_nhwc, return_x3=True), None
-        return self.head(x3, x4, x3a)
+        return ops.dolg_local_pool(self.conv1(x3, x3_amax, self.conv1_b), self.conv2_w, self.conv2_b)
 
     _needs_x3 = True
 
@@ -422,31 +438,25 @@ class SOABlock_GeM:
     caller has none), the attention output's comes from ops.amax_f32."""
 
     def __init__(self, in_ch, k, head, device="cuda", conv_math="h2"):
-        if conv_math not in ("h2", "f32"):
-            raise ValueError("conv_math must be 'h2' or 'f32'")
+        _check_conv_math(conv_math)
         self.in_ch, self.out_ch, self.mid_ch = in_ch, in_ch, in_ch // k
         if tuple(head["fgh_w"].shape) != (3 * self.mid_ch, 1, 1, in_ch) or \
                 tuple(head["v_w"].shape) != (in_ch, 1, 1, self.mid_ch):
             raise ValueError("networks.SOABlock_GeM: head weight shapes do not fit in_ch and k")
         self.device = torch.device(device)
         self.conv_math = conv_math
-        self.fgh_w, self.fgh_b = head["fgh_w"].to(self.device), head["fgh_b"].to(self.device)
-        self.v_w, self.v_b = head["v_w"].to(self.device), head["v_b"].to(self.device)
-        self.fgh_h2 = ops.H2Conv(self.fgh_w) if conv_math == "h2" else None
-        self.v_h2 = ops.H2Conv(self.v_w) if conv_math == "h2" else None
+        self.fgh = HeadConv(head["fgh_w"].to(self.device), conv_math)
+        self.v = HeadConv(head["v_w"].to(self.device), conv_math)
+        self.fgh_b, self.v_b = head["fgh_b"].to(self.device), head["v_b"].to(self.device)
         self.pooling = gem(3.0)
 
     def attended(self, x4, x4_amax=None):
         """z = v(softmax(c^-0.5 f^T g) h^T) + x4, NHWC (:558-567)."""
-        if self.conv_math == "h2":
-            if x4_amax is None:
-                x4_amax = ops.amax_f32(x4, ops.amax_records(1, x4.device)[0])
-            fgh = ops.conv2d_h2(x4, x4_amax, self.fgh_h2, self.fgh_b, 1, 0, None, False)
-            a = ops.soa_attention(fgh, self.mid_ch)
-            a_amax = ops.amax_f32(a, ops.amax_records(1, a.device)[0])
-            return ops.conv2d_h2(a, a_amax, self.v_h2, self.v_b, 1, 0, x4, False)
-        fgh = ops.conv2d(x4, self.fgh_w, self.fgh_b, 1, 0, None, False)
-        return ops.conv2d(ops.soa_attention(fgh, self.mid_ch), self.v_w, self.v_b, 1, 0, x4, False)
+        h2 = self.conv_math == "h2"
+        if h2 and x4_amax is None:
+            x4_amax = ops.amax_of(x4)
+        a = ops.soa_attention(self.fgh(x4, x4_amax, self.fgh_b), self.mid_ch)
+        return self.v(a, ops.amax_of(a) if h2 else None, self.v_b, residual=x4)
 
     def __call__(self, x4, x4_amax=None):
         return self.pooling(self.attended(x4, x4_amax))
@@ -473,10 +483,7 @@ class SOLAR(_Extractor):
             raise ValueError("networks.SOLAR requires outputdim == 2048 (whiten is Conv2d(2048, 2048), "
                              "networks/RetrievalNet.py:577)")
         self.device = torch.device(device)
-        if state_dict is None:
-            head = W.solar_head_from_state_dict(W.synthetic_solar_head(seed + 1))
-        else:
-            head = W.solar_head_from_state_dict(state_dict)
+        head = W.solar_head_from_state_dict(W.synthetic_solar_head(seed + 1) if state_dict is None else state_dict)
         self.backbone = ResNet(backbone, state_dict, seed, device, conv_math, stride_on)
         cin = self.backbone.outputdim_block5
         if head["whiten_w"].shape != (2048, cin):
@@ -487,13 +494,6 @@ class SOLAR(_Extractor):
         self.whiten_b = head["whiten_b"].to(self.device)
         self.outputdim = outputdim
         self.meta = {"outputdim": outputdim}
-
-    def forward_test_nhwc(self, x_nhwc, hook=None):
-        if self.conv_math == "h2":
-            x4, x4a = self.backbone(x_nhwc, hook=hook, return_amax=True)
-        else:
-            x4, x4a = self.backbone(x_nhwc), None
-        return self.tail(self.pooling(x4, x4a))
 
     def _trunk(self):
         return self.backbone
@@ -537,8 +537,7 @@ class Token_Refine:
 
     def __init__(self, num_heads=8, num_object=4, mid_dim=1024, encoder_layer=1, decoder_layer=2, head=None,
                  device="cuda", conv_math="h2"):
-        if conv_math not in ("h2", "f32"):
-            raise ValueError("conv_math must be 'h2' or 'f32'")
+        _check_conv_math(conv_math)
         if mid_dim != 128 * num_heads:
             raise ValueError("networks.Token_Refine: mid_dim must be 128 * num_heads (rr_attention_hd128)")
         if encoder_layer != 1 or decoder_layer != 2:
@@ -552,14 +551,11 @@ class Token_Refine:
         self.device = torch.device(device)
         self.conv_math = conv_math
         self.w = {k: v.to(self.device) for k, v in head.items()}
-        self.h2 = {}
-        if conv_math == "h2":
-            self.h2 = {k: ops.H2Conv(self.w[k + "_w"]) for k in ("conv", "enc_qkv", "enc_proj", "enc_mlp", "dec_kv")}
+        self.convs = {k: HeadConv(self.w[k + "_w"], conv_math)
+                      for k in ("conv", "enc_qkv", "enc_proj", "enc_mlp", "dec_kv")}
 
     def _conv(self, x, xa, name, residual=None, ya=None):
-        if self.conv_math == "h2":
-            return ops.conv2d_h2(x, xa, self.h2[name], self.w[name + "_b"], 1, 0, residual, False, ya)
-        return ops.conv2d(x, self.w[name + "_w"], self.w[name + "_b"], 1, 0, residual, False)
+        return self.convs[name](x, xa, self.w[name + "_b"], residual=residual, y_amax=ya)
 
     def _lin(self, x, name, residual=None):
         return ops.linear_ex(x, self.w[name + "_w"], self.w[name + "_b"], residual)
@@ -628,10 +624,7 @@ class Token(_Extractor):
         if pretrained is not None:
             raise ValueError("networks.Token: pretrained weights cannot be downloaded; pass state_dict")
         self.device = torch.device(device)
-        if state_dict is None:
-            head = W.token_head_from_state_dict(W.synthetic_token_head(seed + 1))
-        else:
-            head = W.token_head_from_state_dict(state_dict)
+        head = W.token_head_from_state_dict(W.synthetic_token_head(seed + 1) if state_dict is None else state_dict)
         self.backbone = ResNet(backbone, state_dict, seed, device, conv_math, stride_on)
         if head["conv_w"].shape[-1] != self.backbone.outputdim_block5:
             raise ValueError("networks.Token: tr.conv does not fit the trunk")
@@ -639,13 +632,6 @@ class Token(_Extractor):
         self.tr = Token_Refine(8, head["query"].shape[0], outputdim, 1, 2, head, device, conv_math)
         self.outputdim = outputdim
         self.meta = {"outputdim": outputdim}
-
-    def forward_test_nhwc(self, x_nhwc, hook=None):
-        if self.conv_math == "h2":
-            x4, x4a = self.backbone(x_nhwc, hook=hook, return_amax=True)
-        else:
-            x4, x4a = self.backbone(x_nhwc), None
-        return self.tail(self.tr(x4, x4a))
 
     def _trunk(self):
         return self.backbone

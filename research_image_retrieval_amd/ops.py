@@ -109,6 +109,11 @@ def amax_f32(x, record):
     return record
 
 
+def amax_of(x):
+    """A fresh record holding max |x|, for a caller of conv2d_h2 that was given none."""
+    return amax_f32(x, amax_records(1, x.device)[0])
+
+
 def amax_value(record):
     """The max a record holds, as a Python float (host read: tests, tools)."""
     return float(record.view(torch.float32).max().item())

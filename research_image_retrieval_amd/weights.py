@@ -9,6 +9,7 @@ versions) so the oracle, the tests and bench.py all rebuild identical weights
 from a seed.
 """
 import collections
+import functools
 import math
 
 import numpy as np
@@ -22,6 +23,43 @@ BN_EPS = 1e-5
 # (conv2), "1x1" = MSRA / pycls, the reference's own torchvision-free R101
 # (networks/backbone.py:310-312: BottleneckTransform.a carries the stride).
 STRIDE_ON = ("3x3", "1x1")
+_BN_KEYS = ("weight", "bias", "running_mean", "running_var")
+
+
+def _t(a):
+    """A numpy array as a contiguous fp32 tensor (the synthetic draws are float64)."""
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+
+
+def _f(a):
+    return a.float().contiguous()
+
+
+def _flat_keys(sd):
+    """sd keyed without a leading ``module.`` and without the wrappers' leading
+    ``backbone.`` after it; of two keys that then meet, the first stays."""
+    flat = {}
+    for k, v in sd.items():
+        for lead in ("module.", "backbone."):
+            if k.startswith(lead):
+                k = k[len(lead):]
+        flat.setdefault(k, v)
+    return flat
+
+
+def _lin(rs, sd, key, out_dim, in_dim, shape=None, gain=1.0, zero_sum=False):
+    """sd[key.weight], sd[key.bias] drawn from rs as PyTorch's default init,
+    U(+-1 / sqrt(in_dim)); the weight (not the bias) gain times wider, each row
+    shifted to sum to zero (zero_sum) and reshaped to shape.  Drawn in blocks
+    of 64 rows so that the float64 draws of the widest layers stay small: the
+    stream, and so every bit, is the same at any block size."""
+    s = 1.0 / np.sqrt(in_dim)
+    w = np.empty((out_dim, in_dim), dtype=np.float32)
+    for r0 in range(0, out_dim, 64):
+        blk = rs.uniform(-1, 1, (min(64, out_dim - r0), in_dim)) * (s * gain)
+        w[r0:r0 + 64] = blk - blk.mean(axis=1, keepdims=True) if zero_sum else blk
+    sd[key + ".weight"] = _t(w.reshape(shape) if shape else w)
+    sd[key + ".bias"] = _t(rs.uniform(-1, 1, out_dim) * s)
 
 
 def block_strides(stride, stride_on):
@@ -240,20 +278,19 @@ def synthetic_dolg_head(seed, c=1024, c4=2048, out_dim=512):
     generator loads them into the
     reference's modules; the tests fold them (dolg_head_from_state_dict)."""
     rs = np.random.RandomState(seed)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
     sd = collections.OrderedDict()
-    sd["localmodel.conv1.weight"] = t(rs.standard_normal((c, c, 1, 1)) * (4.0 / np.sqrt(c)))
-    sd["localmodel.conv1.bias"] = t(rs.standard_normal(c) * 0.1)
-    sd["localmodel.bn.weight"] = t(rs.uniform(0.5, 1.5, c))
-    sd["localmodel.bn.bias"] = t(rs.standard_normal(c) * 0.1)
-    sd["localmodel.bn.running_mean"] = t(rs.standard_normal(c) * 0.1)
-    sd["localmodel.bn.running_var"] = t(rs.uniform(0.5, 1.5, c))
-    sd["localmodel.conv2.weight"] = t(rs.standard_normal((1, c, 1, 1)) * 0.05)
-    sd["localmodel.conv2.bias"] = t(np.full(1, 0.1))
-    sd["fc_t.weight"] = t(rs.uniform(-1, 1, (c, c4)) / np.sqrt(c4))
-    sd["fc_t.bias"] = t(rs.uniform(-1, 1, c) / np.sqrt(c4))
-    sd["fc.weight"] = t(rs.uniform(-1, 1, (out_dim, 2 * c)) / np.sqrt(2 * c))
-    sd["fc.bias"] = t(rs.uniform(-1, 1, out_dim) / np.sqrt(2 * c))
+    sd["localmodel.conv1.weight"] = _t(rs.standard_normal((c, c, 1, 1)) * (4.0 / np.sqrt(c)))
+    sd["localmodel.conv1.bias"] = _t(rs.standard_normal(c) * 0.1)
+    sd["localmodel.bn.weight"] = _t(rs.uniform(0.5, 1.5, c))
+    sd["localmodel.bn.bias"] = _t(rs.standard_normal(c) * 0.1)
+    sd["localmodel.bn.running_mean"] = _t(rs.standard_normal(c) * 0.1)
+    sd["localmodel.bn.running_var"] = _t(rs.uniform(0.5, 1.5, c))
+    sd["localmodel.conv2.weight"] = _t(rs.standard_normal((1, c, 1, 1)) * 0.05)
+    sd["localmodel.conv2.bias"] = _t(np.full(1, 0.1))
+    sd["fc_t.weight"] = _t(rs.uniform(-1, 1, (c, c4)) / np.sqrt(c4))
+    sd["fc_t.bias"] = _t(rs.uniform(-1, 1, c) / np.sqrt(c4))
+    sd["fc.weight"] = _t(rs.uniform(-1, 1, (out_dim, 2 * c)) / np.sqrt(2 * c))
+    sd["fc.bias"] = _t(rs.uniform(-1, 1, out_dim) / np.sqrt(2 * c))
     return sd
 
 
@@ -311,22 +348,21 @@ def synthetic_solar_head(seed, cin=2048, k=2):
     The fixture generator loads them into the reference's modules; the tests
     fold them (solar_head_from_state_dict)."""
     rs = np.random.RandomState(seed)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
     c = cin // k
     sd = collections.OrderedDict()
     for n in "fg":
-        sd[f"pooling.{n}.0.weight"] = t(rs.standard_normal((c, cin, 1, 1)) * (2.0 / np.sqrt(cin)))
-        sd[f"pooling.{n}.0.bias"] = t(rs.standard_normal(c) * 0.1)
-        sd[f"pooling.{n}.1.weight"] = t(rs.uniform(0.5, 1.5, c))
-        sd[f"pooling.{n}.1.bias"] = t(rs.standard_normal(c) * 0.1)
-        sd[f"pooling.{n}.1.running_mean"] = t(rs.standard_normal(c) * 0.1)
-        sd[f"pooling.{n}.1.running_var"] = t(rs.uniform(0.5, 1.5, c))
-    sd["pooling.h.weight"] = t(rs.standard_normal((c, cin, 1, 1)) / np.sqrt(cin))
-    sd["pooling.h.bias"] = t(rs.standard_normal(c) * 0.1)
-    sd["pooling.v.weight"] = t(rs.standard_normal((cin, c, 1, 1)) / np.sqrt(c))
-    sd["pooling.v.bias"] = t(rs.standard_normal(cin) * 0.1)
-    sd["whiten.weight"] = t(rs.uniform(-1, 1, (2048, cin, 1, 1)) / np.sqrt(cin))
-    sd["whiten.bias"] = t(rs.uniform(-1, 1, 2048) / np.sqrt(cin))
+        sd[f"pooling.{n}.0.weight"] = _t(rs.standard_normal((c, cin, 1, 1)) * (2.0 / np.sqrt(cin)))
+        sd[f"pooling.{n}.0.bias"] = _t(rs.standard_normal(c) * 0.1)
+        sd[f"pooling.{n}.1.weight"] = _t(rs.uniform(0.5, 1.5, c))
+        sd[f"pooling.{n}.1.bias"] = _t(rs.standard_normal(c) * 0.1)
+        sd[f"pooling.{n}.1.running_mean"] = _t(rs.standard_normal(c) * 0.1)
+        sd[f"pooling.{n}.1.running_var"] = _t(rs.uniform(0.5, 1.5, c))
+    sd["pooling.h.weight"] = _t(rs.standard_normal((c, cin, 1, 1)) / np.sqrt(cin))
+    sd["pooling.h.bias"] = _t(rs.standard_normal(c) * 0.1)
+    sd["pooling.v.weight"] = _t(rs.standard_normal((cin, c, 1, 1)) / np.sqrt(c))
+    sd["pooling.v.bias"] = _t(rs.standard_normal(cin) * 0.1)
+    sd["whiten.weight"] = _t(rs.uniform(-1, 1, (2048, cin, 1, 1)) / np.sqrt(cin))
+    sd["whiten.bias"] = _t(rs.uniform(-1, 1, 2048) / np.sqrt(cin))
     return sd
 
 
@@ -344,12 +380,7 @@ def how_head_from_state_dict(sd):
       local_w [D,2048] (the 1x1 conv flattened), local_b [D], centroids [K,D],
       weights [K] (ASMK only: its presence says which pooling the head is),
       final_w [2048, K D or K], final_b, cls_w [classes,2048], cls_b."""
-    flat = {}
-    for k, v in sd.items():
-        for lead in ("module.", "backbone."):
-            if k.startswith(lead):
-                k = k[len(lead):]
-        flat.setdefault(k, v)
+    flat = _flat_keys(sd)
     missing = [k for k in HOW_HEAD_KEYS if k not in flat]
     if missing:
         raise ValueError(f"HOW head: missing keys {missing}")
@@ -365,14 +396,13 @@ def how_head_from_state_dict(sd):
         raise ValueError(f"final_proj.weight: expected [out,{pooled}], got {tuple(fw.shape)}")
     if cw.dim() != 2 or cw.shape[1] != fw.shape[0]:
         raise ValueError(f"classifier.weight: expected [classes,{fw.shape[0]}], got {tuple(cw.shape)}")
-    f = lambda a: a.float().contiguous()  # noqa: E731
-    head = {"local_w": f(lw.reshape(lw.shape[0], lw.shape[1])), "local_b": f(flat["local_proj.bias"]),
-            "centroids": f(cent), "final_w": f(fw), "final_b": f(flat["final_proj.bias"]),
-            "cls_w": f(cw), "cls_b": f(flat["classifier.bias"])}
+    head = {"local_w": _f(lw.reshape(lw.shape[0], lw.shape[1])), "local_b": _f(flat["local_proj.bias"]),
+            "centroids": _f(cent), "final_w": _f(fw), "final_b": _f(flat["final_proj.bias"]),
+            "cls_w": _f(cw), "cls_b": _f(flat["classifier.bias"])}
     if asmk:
         if tuple(flat["pooling.weights"].shape) != (cent.shape[0],):
             raise ValueError(f"pooling.weights: expected [{cent.shape[0]}], got {tuple(flat['pooling.weights'].shape)}")
-        head["weights"] = f(flat["pooling.weights"])
+        head["weights"] = _f(flat["pooling.weights"])
     return head
 
 
@@ -389,20 +419,19 @@ def synthetic_how_head(seed, pooling, local_dim=128, num_clusters=64, num_classe
     if pooling not in ("vlad", "asmk"):
         raise ValueError(f"Unsupported pooling type: {pooling}")
     rs = np.random.RandomState(seed)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
     pooled = num_clusters * local_dim if pooling == "vlad" else num_clusters
     sd = collections.OrderedDict()
-    sd["local_proj.weight"] = t(rs.standard_normal((local_dim, 2048, 1, 1)) / np.sqrt(2048))
-    sd["local_proj.bias"] = t(rs.standard_normal(local_dim) * 0.1)
+    sd["local_proj.weight"] = _t(rs.standard_normal((local_dim, 2048, 1, 1)) / np.sqrt(2048))
+    sd["local_proj.bias"] = _t(rs.standard_normal(local_dim) * 0.1)
     c = rs.standard_normal((num_clusters, local_dim))
-    sd["pooling.centroids"] = t(c / np.linalg.norm(c, axis=1, keepdims=True))
+    sd["pooling.centroids"] = _t(c / np.linalg.norm(c, axis=1, keepdims=True))
     if pooling == "asmk":
-        sd["pooling.weights"] = t(0.5 + rs.uniform(0, 1, num_clusters))
+        sd["pooling.weights"] = _t(0.5 + rs.uniform(0, 1, num_clusters))
     s = 1.0 / np.sqrt(pooled)
-    sd["final_proj.weight"] = t(rs.uniform(-1, 1, (2048, pooled)) * s)
-    sd["final_proj.bias"] = t(rs.uniform(-1, 1, 2048) * s)
-    sd["classifier.weight"] = t(rs.uniform(-1, 1, (num_classes, 2048)) / np.sqrt(2048))
-    sd["classifier.bias"] = t(rs.uniform(-1, 1, num_classes) / np.sqrt(2048))
+    sd["final_proj.weight"] = _t(rs.uniform(-1, 1, (2048, pooled)) * s)
+    sd["final_proj.bias"] = _t(rs.uniform(-1, 1, 2048) * s)
+    sd["classifier.weight"] = _t(rs.uniform(-1, 1, (num_classes, 2048)) / np.sqrt(2048))
+    sd["classifier.bias"] = _t(rs.uniform(-1, 1, num_classes) / np.sqrt(2048))
     return sd
 
 
@@ -425,12 +454,7 @@ def sos_head_from_state_dict(sd):
       (absent together: use_attention=False), proj_w [c,2048] (the 1x1 conv
       flattened), proj_b [c], fp0_w [F, c (c + 1) / 2], fp0_b, fp3_w [F,F],
       fp3_b, cls_w [classes,F], cls_b."""
-    flat = {}
-    for k, v in sd.items():
-        for lead in ("module.", "backbone."):
-            if k.startswith(lead):
-                k = k[len(lead):]
-        flat.setdefault(k, v)
+    flat = _flat_keys(sd)
     missing = [k for k in SOS_HEAD_KEYS if k not in flat]
     have_att = [k for k in SOS_ATT_KEYS if k in flat]
     if have_att and len(have_att) != len(SOS_ATT_KEYS):
@@ -448,10 +472,9 @@ def sos_head_from_state_dict(sd):
         raise ValueError(f"feature_proj.3.weight: expected [{f0.shape[0]},{f0.shape[0]}], got {tuple(f3.shape)}")
     if cw.dim() != 2 or cw.shape[1] != f3.shape[0]:
         raise ValueError(f"classifier.weight: expected [classes,{f3.shape[0]}], got {tuple(cw.shape)}")
-    f = lambda a: a.float().contiguous()  # noqa: E731
-    head = {"proj_w": f(pw.reshape(c, pw.shape[1])), "proj_b": f(flat["second_order_pool.proj.bias"]),
-            "fp0_w": f(f0), "fp0_b": f(flat["feature_proj.0.bias"]), "fp3_w": f(f3),
-            "fp3_b": f(flat["feature_proj.3.bias"]), "cls_w": f(cw), "cls_b": f(flat["classifier.bias"])}
+    head = {"proj_w": _f(pw.reshape(c, pw.shape[1])), "proj_b": _f(flat["second_order_pool.proj.bias"]),
+            "fp0_w": _f(f0), "fp0_b": _f(flat["feature_proj.0.bias"]), "fp3_w": _f(f3),
+            "fp3_b": _f(flat["feature_proj.3.bias"]), "cls_w": _f(cw), "cls_b": _f(flat["classifier.bias"])}
     if have_att:
         w1, w2, w3 = (flat[f"similarity_attention.attention_net.{i}.weight"] for i in (0, 2, 4))
         if w1.dim() != 2 or w1.shape[1] != pw.shape[1]:
@@ -460,8 +483,8 @@ def sos_head_from_state_dict(sd):
         if w2.dim() != 2 or w2.shape[1] != w1.shape[0] or tuple(w3.shape) != (1, w2.shape[0]):
             raise ValueError("similarity_attention.attention_net: expected [H/2,H] and [1,H/2] after [H,Cin], got "
                              f"{tuple(w2.shape)} and {tuple(w3.shape)}")
-        head.update(att_w1=f(w1), att_b1=f(flat[SOS_ATT_KEYS[1]]), att_w2=f(w2), att_b2=f(flat[SOS_ATT_KEYS[3]]),
-                    att_w3=f(w3.reshape(-1)), att_b3=f(flat[SOS_ATT_KEYS[5]].reshape(1)))
+        head.update(att_w1=_f(w1), att_b1=_f(flat[SOS_ATT_KEYS[1]]), att_w2=_f(w2), att_b2=_f(flat[SOS_ATT_KEYS[3]]),
+                    att_w3=_f(w3.reshape(-1)), att_b3=_f(flat[SOS_ATT_KEYS[5]].reshape(1)))
     return head
 
 
@@ -477,18 +500,8 @@ def synthetic_sos_head(seed, second_order_dim=512, num_classes=8, use_attention=
     logit one way (a within 0.0001-0.74 at one seed); zero-sum weights centre
     the logits and a spans [<= 0.2, >= 0.8] on a 7 x 7 map."""
     rs = np.random.RandomState(seed)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
     sd = collections.OrderedDict()
-
-    def lin(key, out_dim, in_dim, gain=1.0, shape=None, zero_sum=False):
-        s = 1.0 / np.sqrt(in_dim)
-        w = np.empty((out_dim, in_dim), dtype=np.float32)
-        for r0 in range(0, out_dim, 256):  # row blocks: the float64 draws of the widest layer stay small
-            blk = rs.uniform(-1, 1, (min(256, out_dim - r0), in_dim)) * (s * gain)
-            w[r0:r0 + 256] = blk - blk.mean(axis=1, keepdims=True) if zero_sum else blk
-        sd[key + ".weight"] = t(w.reshape(shape) if shape else w)
-        sd[key + ".bias"] = t(rs.uniform(-1, 1, out_dim) * s)
-
+    lin = functools.partial(_lin, rs, sd)
     c = second_order_dim
     if use_attention:
         lin("similarity_attention.attention_net.0", 512, 2048)
@@ -502,7 +515,6 @@ def synthetic_sos_head(seed, second_order_dim=512, num_classes=8, use_attention=
 
 
 # ---- SpoC head (models/spoc.py:52-147) --------------------------------------
-_BN_KEYS = ("weight", "bias", "running_mean", "running_var")
 _CA = "contextual_attention."
 SPOC_CTX_KEYS = tuple(f"{_CA}context_encoder.{i}.{k}" for i in (0, 3) for k in ("weight", "bias")) + \
     tuple(f"{_CA}context_encoder.{i}.{k}" for i in (1, 4) for k in _BN_KEYS) + \
@@ -541,19 +553,13 @@ def spoc_head_from_state_dict(sd, eps=BN_EPS):
       contextual_attention keys absent together: use_context=False);
       agg_w [F,C], agg_b [F] (Conv1d(1) + BatchNorm1d); fp0_w [F,F], fp0_b,
       fp3_w [F,F], fp3_b; cls_w [classes,F], cls_b."""
-    flat = {}
-    for k, v in sd.items():
-        for lead in ("module.", "backbone."):
-            if k.startswith(lead):
-                k = k[len(lead):]
-        flat.setdefault(k, v)
+    flat = _flat_keys(sd)
     missing = [k for k in SPOC_HEAD_KEYS if k not in flat]
     have_ctx = [k for k in SPOC_CTX_KEYS if k in flat]
     if have_ctx and len(have_ctx) != len(SPOC_CTX_KEYS):
         missing += [k for k in SPOC_CTX_KEYS if k not in flat]
     if missing:
         raise ValueError(f"SpoC head: missing keys {missing}")
-    f = lambda a: a.float().contiguous()  # noqa: E731
     aw, f0, f3, cw = (flat[k] for k in ("feature_aggregation.0.weight", "feature_proj.0.weight",
                                         "feature_proj.3.weight", "classifier.weight"))
     if aw.dim() != 3 or aw.shape[2] != 1:
@@ -570,8 +576,9 @@ def spoc_head_from_state_dict(sd, eps=BN_EPS):
         if tuple(flat[k].shape) != (n,):
             raise ValueError(f"{k}: expected [{n}], got {tuple(flat[k].shape)}")
     wa, ba = _fold_bn_biased(aw.reshape(fd, c), flat["feature_aggregation.0.bias"], flat, "feature_aggregation.1", eps)
-    head = {"agg_w": f(wa), "agg_b": f(ba), "fp0_w": f(f0), "fp0_b": f(flat["feature_proj.0.bias"]), "fp3_w": f(f3),
-            "fp3_b": f(flat["feature_proj.3.bias"]), "cls_w": f(cw), "cls_b": f(flat["classifier.bias"])}
+    head = {"agg_w": _f(wa), "agg_b": _f(ba), "fp0_w": _f(f0), "fp0_b": _f(flat["feature_proj.0.bias"]),
+            "fp3_w": _f(f3), "fp3_b": _f(flat["feature_proj.3.bias"]), "cls_w": _f(cw),
+            "cls_b": _f(flat["classifier.bias"])}
     if have_ctx:
         enc = _CA + "context_encoder."
         w0, w1 = flat[enc + "0.weight"], flat[enc + "3.weight"]
@@ -593,10 +600,10 @@ def spoc_head_from_state_dict(sd, eps=BN_EPS):
         wf0, bf0 = _fold_bn_biased(w0, flat[enc + "0.bias"], flat, enc + "1", eps)
         wf1, bf1 = _fold_bn_biased(w1, flat[enc + "3.bias"], flat, enc + "4", eps)
         wr2 = wr.reshape(c, c + dc)
-        head.update(ce0_w=f(wf0.permute(0, 2, 3, 1)), ce0_b=f(bf0), ce1_w=f(wf1.permute(0, 2, 3, 1)), ce1_b=f(bf1),
-                    att_w=f(wt.reshape(dc)), att_b=float(flat[_CA + "attention_conv.bias"].reshape(())),
-                    refine_wx=f(wr2[:, :c]).reshape(c, 1, 1, c), refine_wc=f(wr2[:, c:]),
-                    refine_b=f(flat[_CA + "feature_refine.bias"]))
+        head.update(ce0_w=_f(wf0.permute(0, 2, 3, 1)), ce0_b=_f(bf0), ce1_w=_f(wf1.permute(0, 2, 3, 1)), ce1_b=_f(bf1),
+                    att_w=_f(wt.reshape(dc)), att_b=float(flat[_CA + "attention_conv.bias"].reshape(())),
+                    refine_wx=_f(wr2[:, :c]).reshape(c, 1, 1, c), refine_wc=_f(wr2[:, c:]),
+                    refine_b=_f(flat[_CA + "feature_refine.bias"]))
     return head
 
 
@@ -616,24 +623,15 @@ def synthetic_spoc_head(seed, context_dim=512, num_classes=8, use_context=True, 
     pre-activations, and ReLU clips every region in some columns (an exact 0
     in agg, the pad-row trap of rr_linear_groupmax)."""
     rs = np.random.RandomState(seed)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
     sd = collections.OrderedDict()
     c = 2048
-
-    def lin(key, out_dim, in_dim, shape=None, gain=1.0, zero_sum=False):
-        s = 1.0 / np.sqrt(in_dim)
-        w = np.empty((out_dim, in_dim), dtype=np.float32)
-        for r0 in range(0, out_dim, 64):  # row blocks: the float64 draws of the 3x3 convs stay small
-            blk = rs.uniform(-1, 1, (min(64, out_dim - r0), in_dim)) * (s * gain)
-            w[r0:r0 + 64] = blk - blk.mean(axis=1, keepdims=True) if zero_sum else blk
-        sd[key + ".weight"] = t(w.reshape(shape) if shape else w)
-        sd[key + ".bias"] = t(rs.uniform(-1, 1, out_dim) * s)
+    lin = functools.partial(_lin, rs, sd)
 
     def bn(key, n):
-        sd[key + ".weight"] = t(rs.uniform(0.5, 1.5, n))
-        sd[key + ".bias"] = t(rs.standard_normal(n) * 0.1)
-        sd[key + ".running_mean"] = t(rs.standard_normal(n) * 0.1)
-        sd[key + ".running_var"] = t(rs.uniform(0.5, 1.5, n))
+        sd[key + ".weight"] = _t(rs.uniform(0.5, 1.5, n))
+        sd[key + ".bias"] = _t(rs.standard_normal(n) * 0.1)
+        sd[key + ".running_mean"] = _t(rs.standard_normal(n) * 0.1)
+        sd[key + ".running_var"] = _t(rs.uniform(0.5, 1.5, n))
 
     dc = context_dim
     if use_context:
@@ -700,31 +698,25 @@ def tokagg_head_from_state_dict(sd):
       fp_w [F,Cin], fp_b, cls_w [classes,F], cls_b.
 
     The layer count is the number of consecutive transformer.layers.{i} found."""
-    flat = {}
-    for k, v in sd.items():
-        for lead in ("module.", "backbone."):
-            if k.startswith(lead):
-                k = k[len(lead):]
-        flat.setdefault(k, v)
+    flat = _flat_keys(sd)
     layers = 0
     while any(f"{_TA}transformer.layers.{layers}.{k}" in flat for k in TOKAGG_LAYER_KEYS):
         layers += 1
     missing = [k for k in tokagg_head_keys(max(layers, 1)) if k not in flat]
     if missing:
         raise ValueError(f"token aggregator head: missing keys {missing}")
-    f = lambda a: a.float().contiguous()  # noqa: E731
     in_w, gt = flat[_TA + "input_proj.weight"], flat[_TA + "global_token"]
     if in_w.dim() != 2:
         raise ValueError(f"token_aggregator.input_proj.weight: expected [d,Cin], got {tuple(in_w.shape)}")
     d, cin = in_w.shape
     if gt.numel() != d:
         raise ValueError(f"token_aggregator.global_token: expected {d} values, got {tuple(gt.shape)}")
-    head = {"in_w": f(in_w), "in_b": f(flat[_TA + "input_proj.bias"]), "global_token": f(gt.reshape(d))}
+    head = {"in_w": _f(in_w), "in_b": _f(flat[_TA + "input_proj.bias"]), "global_token": _f(gt.reshape(d))}
     if TOKAGG_PE_KEY in flat:
         pe = flat[TOKAGG_PE_KEY]
         if pe.dim() != 3 or pe.shape[1] != 1 or pe.shape[2] != d:
             raise ValueError(f"token_aggregator.pos_encoding.pe: expected [max_len,1,{d}], got {tuple(pe.shape)}")
-        head["pe"] = f(pe.reshape(pe.shape[0], d))
+        head["pe"] = _f(pe.reshape(pe.shape[0], d))
     else:
         head["pe"] = tokagg_positional_encoding(d)
     for i in range(layers):
@@ -737,7 +729,7 @@ def tokagg_head_from_state_dict(sd):
             t = flat[pre + key]
             if tuple(t.shape) != shapes[name]:
                 raise ValueError(f"{pre + key}: expected {list(shapes[name])}, got {tuple(t.shape)}")
-            head[f"l{i}_{name}"] = f(t)
+            head[f"l{i}_{name}"] = _f(t)
     ow, fw, cw = flat[_TA + "output_proj.weight"], flat["feature_proj.weight"], flat["classifier.weight"]
     if ow.dim() != 2 or ow.shape[1] != d or ow.shape[0] != cin:
         raise ValueError(f"token_aggregator.output_proj.weight: expected [{cin},{d}], got {tuple(ow.shape)}")
@@ -745,8 +737,8 @@ def tokagg_head_from_state_dict(sd):
         raise ValueError(f"feature_proj.weight: expected [F,{cin}], got {tuple(fw.shape)}")
     if cw.dim() != 2 or cw.shape[1] != fw.shape[0]:
         raise ValueError(f"classifier.weight: expected [classes,{fw.shape[0]}], got {tuple(cw.shape)}")
-    head.update(op_w=f(ow), op_b=f(flat[_TA + "output_proj.bias"]), fp_w=f(fw), fp_b=f(flat["feature_proj.bias"]),
-                cls_w=f(cw), cls_b=f(flat["classifier.bias"]))
+    head.update(op_w=_f(ow), op_b=_f(flat[_TA + "output_proj.bias"]), fp_w=_f(fw), fp_b=_f(flat["feature_proj.bias"]),
+                cls_w=_f(cw), cls_b=_f(flat["classifier.bias"]))
     return head
 
 
@@ -787,8 +779,9 @@ def tokagg_fold_last_layer(layer, heads, dtype=torch.float32):
     a0 = torch.bmm(wk.transpose(1, 2), bq.unsqueeze(2)).squeeze(2) * s
     m = torch.bmm(wo.view(d, heads, e).permute(1, 0, 2), wv)       # [heads, d, d]: Wo[:, h] Wv_h
     m0 = wo @ bv + bo
-    f = lambda t: t.to(dtype).contiguous()  # noqa: E731
-    return f(a.reshape(heads * d, d)), f(a0.reshape(heads * d)), f(m.permute(1, 0, 2).reshape(d, heads * d)), f(m0)
+    out = lambda v: v.to(dtype).contiguous()  # noqa: E731
+    return (out(a.reshape(heads * d, d)), out(a0.reshape(heads * d)), out(m.permute(1, 0, 2).reshape(d, heads * d)),
+            out(m0))
 
 
 def synthetic_tokagg_head(seed, hidden_dim=512, num_heads=8, num_layers=2, num_classes=8, feature_dim=2048,
@@ -812,29 +805,23 @@ def synthetic_tokagg_head(seed, hidden_dim=512, num_heads=8, num_layers=2, num_c
     if hidden_dim % num_heads:
         raise ValueError("synthetic_tokagg_head: num_heads must divide hidden_dim")
     rs = np.random.RandomState(seed)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
     sd = collections.OrderedDict()
     d = hidden_dim
-
-    def lin(key, out_dim, in_d):
-        s = 1.0 / np.sqrt(in_d)
-        sd[key + ".weight"] = t(rs.uniform(-1, 1, (out_dim, in_d)) * s)
-        sd[key + ".bias"] = t(rs.uniform(-1, 1, out_dim) * s)
-
+    lin = functools.partial(_lin, rs, sd)
     lin(_TA + "input_proj", d, in_dim)
-    sd[_TA + "global_token"] = t(rs.standard_normal((1, 1, d)))
+    sd[_TA + "global_token"] = _t(rs.standard_normal((1, 1, d)))
     for i in range(num_layers):
         pre = f"{_TA}transformer.layers.{i}."
         w = rs.uniform(-1, 1, (3 * d, d)) * np.sqrt(6.0 / (4 * d))
         w[:2 * d] *= qk_gain
-        sd[pre + "self_attn.in_proj_weight"] = t(w)
-        sd[pre + "self_attn.in_proj_bias"] = t(rs.uniform(-1, 1, 3 * d) / np.sqrt(d))
+        sd[pre + "self_attn.in_proj_weight"] = _t(w)
+        sd[pre + "self_attn.in_proj_bias"] = _t(rs.uniform(-1, 1, 3 * d) / np.sqrt(d))
         lin(pre + "self_attn.out_proj", d, d)
         lin(pre + "linear1", 4 * d, d)
         lin(pre + "linear2", d, 4 * d)
         for n in ("norm1", "norm2"):
-            sd[pre + n + ".weight"] = t(1 + 0.1 * rs.uniform(-1, 1, d))
-            sd[pre + n + ".bias"] = t(0.1 * rs.uniform(-1, 1, d))
+            sd[pre + n + ".weight"] = _t(1 + 0.1 * rs.uniform(-1, 1, d))
+            sd[pre + n + ".bias"] = _t(0.1 * rs.uniform(-1, 1, d))
     lin(_TA + "output_proj", in_dim, d)
     lin("feature_proj", feature_dim, in_dim)
     lin("classifier", num_classes, feature_dim)
@@ -842,7 +829,6 @@ def synthetic_tokagg_head(seed, hidden_dim=512, num_heads=8, num_layers=2, num_c
 
 
 # ---- Token head (networks/RetrievalNet.py:94-187) ---------------------------
-_BN_KEYS =("weight", "bias", "running_mean", "running_var")
 _WB = ("weight", "bias")
 _ATT = tuple(f"{p}.{k}" for p in ("q", "k", "v", "proj") for k in _WB)
 
@@ -888,7 +874,6 @@ def token_head_from_state_dict(sd, eps=BN_EPS):
     if missing:
         raise ValueError(f"Token head: missing keys {missing}")
     d = lambda k: sd["tr." + k].double()  # noqa: E731
-    f = lambda a: a.float().contiguous()  # noqa: E731
     cw = sd["tr.conv.0.weight"]
     if cw.dim() != 4 or tuple(cw.shape[2:]) != (1, 1):
         raise ValueError(f"tr.conv.0.weight: expected [mid,2048,1,1], got {tuple(cw.shape)}")
@@ -917,37 +902,37 @@ def token_head_from_state_dict(sd, eps=BN_EPS):
         s = d(p + ".weight") / torch.sqrt(d(p + ".running_var") + eps)
         return s, d(p + ".bias") - d(p + ".running_mean") * s
 
-    as_conv = lambda w: f(w).reshape(w.shape[0], 1, 1, w.shape[1])  # noqa: E731
+    as_conv = lambda w: _f(w).reshape(w.shape[0], 1, 1, w.shape[1])  # noqa: E731
     cat = lambda ks: torch.cat([d(k) for k in ks])  # noqa: E731
     h = {}
     s, t = bn("conv.1")
-    h["conv_w"] = f((d("conv.0.weight") * s[:, None, None, None]).permute(0, 2, 3, 1))
-    h["conv_b"] = f(d("conv.0.bias") * s + t)
+    h["conv_w"] = _f((d("conv.0.weight") * s[:, None, None, None]).permute(0, 2, 3, 1))
+    h["conv_b"] = _f(d("conv.0.bias") * s + t)
     e = "encoder.0."
     h["enc_qkv_w"] = as_conv(cat([e + f"attn.{p}.weight" for p in "qkv"]))
-    h["enc_qkv_b"] = f(cat([e + f"attn.{p}.bias" for p in "qkv"]))
-    h["enc_proj_w"], h["enc_proj_b"] = as_conv(d(e + "attn.proj.weight")), f(d(e + "attn.proj.bias"))
+    h["enc_qkv_b"] = _f(cat([e + f"attn.{p}.bias" for p in "qkv"]))
+    h["enc_proj_w"], h["enc_proj_b"] = as_conv(d(e + "attn.proj.weight")), _f(d(e + "attn.proj.bias"))
     s, t = bn(e + "bn")
     h["enc_mlp_w"] = as_conv(d(e + "mlp.weight") * s[None, :])
-    h["enc_mlp_b"] = f(d(e + "mlp.bias") + d(e + "mlp.weight") @ t)
-    h["query"] = f(qy[0])
-    h["tn_w"], h["tn_b"] = f(d("token_norm.0.weight")), f(d("token_norm.0.bias"))
-    h["tn_g"], h["tn_beta"] = f(d("token_norm.1.weight")), f(d("token_norm.1.bias"))
+    h["enc_mlp_b"] = _f(d(e + "mlp.bias") + d(e + "mlp.weight") @ t)
+    h["query"] = _f(qy[0])
+    h["tn_w"], h["tn_b"] = _f(d("token_norm.0.weight")), _f(d("token_norm.0.bias"))
+    h["tn_g"], h["tn_beta"] = _f(d("token_norm.1.weight")), _f(d("token_norm.1.bias"))
     kv = [f"decoder.{i}.cross_attn.{p}" for i in (0, 1) for p in "kv"]
     h["dec_kv_w"] = as_conv(cat([k + ".weight" for k in kv]))
-    h["dec_kv_b"] = f(cat([k + ".bias" for k in kv]))
+    h["dec_kv_b"] = _f(cat([k + ".bias" for k in kv]))
     for i in (0, 1):
         p, o = f"decoder.{i}.", f"d{i}_"
         for src, dst in (("bn1", "ln1"), ("bn2", "ln2")):
-            h[o + dst + "_g"], h[o + dst + "_b"] = f(d(p + src + ".weight")), f(d(p + src + ".bias"))
+            h[o + dst + "_g"], h[o + dst + "_b"] = _f(d(p + src + ".weight")), _f(d(p + src + ".bias"))
         for src, dst in (("cross_attn.q", "cq"), ("cross_attn.proj", "cproj"), ("mlp.fc1", "fc1"), ("mlp.fc2", "fc2"),
                          ("self_attn.proj", "sproj")):
-            h[o + dst + "_w"], h[o + dst + "_b"] = f(d(p + src + ".weight")), f(d(p + src + ".bias"))
-        h[o + "sqkv_w"] = f(cat([p + f"self_attn.{n}.weight" for n in "qkv"]))
-        h[o + "sqkv_b"] = f(cat([p + f"self_attn.{n}.bias" for n in "qkv"]))
+            h[o + dst + "_w"], h[o + dst + "_b"] = _f(d(p + src + ".weight")), _f(d(p + src + ".bias"))
+        h[o + "sqkv_w"] = _f(cat([p + f"self_attn.{n}.weight" for n in "qkv"]))
+        h[o + "sqkv_b"] = _f(cat([p + f"self_attn.{n}.bias" for n in "qkv"]))
     s, t = bn("proj.1")
-    h["out_w"] = f(d("proj.0.weight") * s[:, None])
-    h["out_b"] = f(d("proj.0.bias") * s + t)
+    h["out_w"] = _f(d("proj.0.weight") * s[:, None])
+    h["out_b"] = _f(d("proj.0.bias") * s + t)
     return h
 
 
@@ -961,20 +946,19 @@ def synthetic_token_head(seed, mid_dim=1024, n_obj=4):
     generator loads them into the reference's modules; the tests fold them
     (token_head_from_state_dict)."""
     rs = np.random.RandomState(seed)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
     m = mid_dim
     sd = collections.OrderedDict()
 
     def lin(key, out_dim, in_dim, gain=1.0, bias=0.1):
-        sd[key + ".weight"] = t(rs.standard_normal((out_dim, in_dim)) * (gain / np.sqrt(in_dim)))
-        sd[key + ".bias"] = t(rs.standard_normal(out_dim) * bias)
+        sd[key + ".weight"] = _t(rs.standard_normal((out_dim, in_dim)) * (gain / np.sqrt(in_dim)))
+        sd[key + ".bias"] = _t(rs.standard_normal(out_dim) * bias)
 
     def norm(key, dim, stats):
-        sd[key + ".weight"] = t(rs.uniform(0.5, 1.5, dim))
-        sd[key + ".bias"] = t(rs.standard_normal(dim) * 0.1)
+        sd[key + ".weight"] = _t(rs.uniform(0.5, 1.5, dim))
+        sd[key + ".bias"] = _t(rs.standard_normal(dim) * 0.1)
         if stats:
-            sd[key + ".running_mean"] = t(rs.standard_normal(dim) * 0.1)
-            sd[key + ".running_var"] = t(rs.uniform(0.5, 1.5, dim))
+            sd[key + ".running_mean"] = _t(rs.standard_normal(dim) * 0.1)
+            sd[key + ".running_var"] = _t(rs.uniform(0.5, 1.5, dim))
 
     def attention(key, qk_gain):
         lin(key + ".q", m, m, qk_gain)
@@ -982,7 +966,7 @@ def synthetic_token_head(seed, mid_dim=1024, n_obj=4):
         lin(key + ".v", m, m)
         lin(key + ".proj", m, m)
 
-    sd["tr.query"] = t(rs.standard_normal((1, n_obj, m)) * (2.0 / np.sqrt(m)))
+    sd["tr.query"] = _t(rs.standard_normal((1, n_obj, m)) * (2.0 / np.sqrt(m)))
     lin("tr.token_norm.0", m, m)
     norm("tr.token_norm.1", m, False)
     attention("tr.encoder.0.attn", 2.0)
@@ -996,8 +980,8 @@ def synthetic_token_head(seed, mid_dim=1024, n_obj=4):
         norm(d + "bn2", m, False)
         lin(d + "mlp.fc1", 2 * m, m)
         lin(d + "mlp.fc2", m, 2 * m)
-    sd["tr.conv.0.weight"] = t(rs.standard_normal((m, 2048, 1, 1)) / np.sqrt(2048))
-    sd["tr.conv.0.bias"] = t(rs.standard_normal(m) * 0.1)
+    sd["tr.conv.0.weight"] = _t(rs.standard_normal((m, 2048, 1, 1)) / np.sqrt(2048))
+    sd["tr.conv.0.bias"] = _t(rs.standard_normal(m) * 0.1)
     norm("tr.conv.1", m, True)
     lin("tr.proj.0", 1024, n_obj * m)
     norm("tr.proj.1", 1024, True)
@@ -1007,7 +991,7 @@ def synthetic_token_head(seed, mid_dim=1024, n_obj=4):
 def folded_resnet(sd, arch):
     """torchvision-keyed trunk -> ordered list of folded (name, w, b, stride, pad)."""
     def bn(prefix):
-        return {k: sd[f"{prefix}.{k}"] for k in ("weight", "bias", "running_mean", "running_var")}
+        return {k: sd[f"{prefix}.{k}"] for k in _BN_KEYS}
 
     out = collections.OrderedDict()
     for conv, bnp, cout, cin, k in resnet_conv_specs(arch):
@@ -1094,26 +1078,25 @@ def synthetic_vit_state_dict(width=768, layers=12, heads=12, patch=16, res=224, 
     """Seeded CLIP-layout ViT weights (networks/model.py:206-243 key names)."""
     rs = np.random.RandomState(seed)
     sc = width ** -0.5
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
     sd = collections.OrderedDict()
-    sd["conv1.weight"] = t(rs.standard_normal((width, 3, patch, patch)) / np.sqrt(3 * patch * patch))
-    sd["class_embedding"] = t(rs.standard_normal(width) * sc)
-    sd["positional_embedding"] = t(rs.standard_normal(((res // patch) ** 2 + 1, width)) * sc)
-    sd["ln_pre.weight"], sd["ln_pre.bias"] = t(np.ones(width)), t(np.zeros(width))
+    sd["conv1.weight"] = _t(rs.standard_normal((width, 3, patch, patch)) / np.sqrt(3 * patch * patch))
+    sd["class_embedding"] = _t(rs.standard_normal(width) * sc)
+    sd["positional_embedding"] = _t(rs.standard_normal(((res // patch) ** 2 + 1, width)) * sc)
+    sd["ln_pre.weight"], sd["ln_pre.bias"] = _t(np.ones(width)), _t(np.zeros(width))
     for i in range(layers):
         p = f"transformer.resblocks.{i}."
-        sd[p + "attn.in_proj_weight"] = t(rs.standard_normal((3 * width, width)) * sc)
-        sd[p + "attn.in_proj_bias"] = t(np.zeros(3 * width))
-        sd[p + "attn.out_proj.weight"] = t(rs.standard_normal((width, width)) * sc)
-        sd[p + "attn.out_proj.bias"] = t(np.zeros(width))
-        sd[p + "ln_1.weight"], sd[p + "ln_1.bias"] = t(np.ones(width)), t(np.zeros(width))
-        sd[p + "mlp.c_fc.weight"] = t(rs.standard_normal((4 * width, width)) * sc)
-        sd[p + "mlp.c_fc.bias"] = t(np.zeros(4 * width))
-        sd[p + "mlp.c_proj.weight"] = t(rs.standard_normal((width, 4 * width)) * (0.5 / np.sqrt(4 * width)))
-        sd[p + "mlp.c_proj.bias"] = t(np.zeros(width))
-        sd[p + "ln_2.weight"], sd[p + "ln_2.bias"] = t(np.ones(width)), t(np.zeros(width))
-    sd["ln_post.weight"], sd["ln_post.bias"] = t(np.ones(width)), t(np.zeros(width))
-    sd["proj"] = t(rs.standard_normal((width, out_dim)) * sc)
+        sd[p + "attn.in_proj_weight"] = _t(rs.standard_normal((3 * width, width)) * sc)
+        sd[p + "attn.in_proj_bias"] = _t(np.zeros(3 * width))
+        sd[p + "attn.out_proj.weight"] = _t(rs.standard_normal((width, width)) * sc)
+        sd[p + "attn.out_proj.bias"] = _t(np.zeros(width))
+        sd[p + "ln_1.weight"], sd[p + "ln_1.bias"] = _t(np.ones(width)), _t(np.zeros(width))
+        sd[p + "mlp.c_fc.weight"] = _t(rs.standard_normal((4 * width, width)) * sc)
+        sd[p + "mlp.c_fc.bias"] = _t(np.zeros(4 * width))
+        sd[p + "mlp.c_proj.weight"] = _t(rs.standard_normal((width, 4 * width)) * (0.5 / np.sqrt(4 * width)))
+        sd[p + "mlp.c_proj.bias"] = _t(np.zeros(width))
+        sd[p + "ln_2.weight"], sd[p + "ln_2.bias"] = _t(np.ones(width)), _t(np.zeros(width))
+    sd["ln_post.weight"], sd["ln_post.bias"] = _t(np.ones(width)), _t(np.zeros(width))
+    sd["proj"] = _t(rs.standard_normal((width, out_dim)) * sc)
     return sd
 
 

@@ -402,7 +402,9 @@ def test_how_entry_points_agree(cuda, nets, pooling):
     xn = x.permute(0, 3, 1, 2).contiguous()
     a = net.forward_test(xn)
     assert a.shape == (4, 2048)
-    assert _bits_equal(a, net.forward_test_u8(imgs.to(cuda)))
+    u8 = net.forward_test_u8(imgs.to(cuda))
+    assert _bits_equal(a, u8)
+    assert _bits_equal(net.backbone.forward_test_u8(imgs.to(cuda)), u8)  # the model's own, not only the wrapper's
     assert _bits_equal(a, net.extract_global_descriptor(xn)) and _bits_equal(a, net.extract_descriptor(xn))
     assert _bits_equal(extract_vectors(net, [imgs[:2], imgs[2:]], ms=[1], device=cuda, print_freq=0).to(cuda),
                        torch.cat([net.forward_test_u8(imgs[:2].to(cuda)), net.forward_test_u8(imgs[2:].to(cuda))]))

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from research_image_retrieval_amd.networks import GeM, GeMPCAw, ConvDimReduction
-from research_image_retrieval_amd import weights as W
+from research_image_retrieval_amd import models, weights as W
 
 pytestmark = pytest.mark.gpu
 
@@ -35,6 +35,18 @@ def test_streams_bit_identical_to_serial_parts(parts, lag, batch):
         assert torch.equal(out.view(torch.int32), ref.view(torch.int32))
     whole = net.forward_test_u8(imgs)
     assert (out - whole).abs().max().item() <= 1e-6
+
+
+def test_streams_through_a_model_wrapper():
+    """models.GeMWrapper hands the gate's hook on to its model's trunk: two
+    streams, lag 1, 4 images of 64 x 64 against the two halves in turn."""
+    dev = torch.device("cuda:0")
+    net = models.GeMWrapper(8, backbone="resnet50", seed=3, device=dev)
+    imgs = torch.from_numpy(np.random.RandomState(5).randint(0, 256, size=(4, 64, 64, 3), dtype=np.uint8)).to(dev)
+    ref = torch.cat([net.forward_test_u8(imgs[:2]), net.forward_test_u8(imgs[2:])])
+    out = net.forward_test_u8_streams(imgs, [torch.cuda.Stream(dev) for _ in range(2)], lag=1)
+    assert out.shape == (4, 2048)
+    assert torch.equal(out.view(torch.int32), ref.view(torch.int32))
 
 
 def test_streams_empty_part():

@@ -424,7 +424,7 @@ def test_spoc_vs_reference(cuda, fx, nets, head, tag):
     for cm in ("f32", "h2"):
         net = nets(cm).backbone
         x = net._input(I.trunk_input(seed, b, h, w).to(cuda))
-        x4, x4a = net._trunk(x)
+        x4, x4a = net.trunk_map(x)
         got = ops.l2_normalize(net.head(x4, x4a), 1e-12).cpu().double()
         x4c = x4.permute(0, 3, 1, 2).contiguous().cpu()
         r64, r32 = spoc_ref.head_forward(x4c, head, torch.float64), spoc_ref.head_forward(x4c, head, torch.float32)
@@ -454,7 +454,9 @@ def test_spoc_entry_points_agree(cuda, nets):
     a = net.forward_test(xn)
     assert a.shape == (4, 2048)
     assert bool(((a.double().norm(dim=1) - 1.0).abs() < 1e-5).all())
-    assert _bits_equal(a, net.forward_test_u8(imgs.to(cuda)))
+    u8 = net.forward_test_u8(imgs.to(cuda))
+    assert _bits_equal(a, u8)
+    assert _bits_equal(net.backbone.forward_test_u8(imgs.to(cuda)), u8)  # the model's own, not only the wrapper's
     assert _bits_equal(a, net.extract_global_descriptor(xn)) and _bits_equal(a, net.extract_descriptor(xn))
     assert _bits_equal(extract_vectors(net, [imgs[:2], imgs[2:]], ms=[1], device=cuda, print_freq=0).to(cuda),
                        torch.cat([net.forward_test_u8(imgs[:2].to(cuda)), net.forward_test_u8(imgs[2:].to(cuda))]))

@@ -54,8 +54,8 @@ def main():
     net = DOLG(seed=3, device=dev, conv_math="h2")
     x = torch.randn((a.batch, a.size, a.size, 4), device=dev, generator=g)
     x[..., 3] = 0
-    trunk = lambda: net.globalmodel(x, return_x3=True, return_x3_amax=True)  # noqa: E731
-    x3, x4, x3a = trunk()
+    trunk = lambda: net.globalmodel.maps(x, want_x3=True)  # noqa: E731
+    x3, x4, x3a, _ = trunk()
     for r in range(a.rounds):
         tt = t_ms(trunk, 5, warm=1)
         th = t_ms(lambda: net.head(x3, x4, x3a), 20, warm=1)

@@ -115,7 +115,7 @@ def main():
         for cls in (models.HOWVLADWrapper, models.HOWASMKWrapper):
             net = cls(8, backbone="resnet50", seed=3, device=dev, conv_math=a.conv_math)
             m = net.backbone
-            x4, x4a = m._trunk(xn)
+            x4, x4a = m.trunk_map(xn)
             t = alternated({"how": lambda: net.forward_test(x), "gem": lambda: gem.forward_test(x),
                             "head": lambda: m.head(x4, x4a)}, a.rounds, a.iters)
             print(f"B={b} {h}x{w} R50 {a.conv_math}: {cls.__name__}.forward_test {t['how']:.3f} ms | "

@@ -58,21 +58,13 @@ def main():
     for b, h, w in ((64, 224, 224), (1, 768, 1024)):
         x = torch.randn((b, 3, h, w), device=dev, generator=g)
         xn = ops.nchw_to_nhwc(x, out_c=4)
-        if a.conv_math == "h2":
-            x4, x4a = solar.backbone(xn, return_amax=True)
-            fgh = ops.conv2d_h2(x4, x4a, blk.fgh_h2, blk.fgh_b, 1, 0, None, False)
-        else:
-            x4, x4a = solar.backbone(xn), None
-            fgh = ops.conv2d(x4, blk.fgh_w, blk.fgh_b, 1, 0, None, False)
+        _, x4, _, x4a = solar.backbone.maps(xn)
+        fgh_leg = lambda: blk.fgh(x4, x4a, blk.fgh_b)  # noqa: E731
+        fgh = fgh_leg()
         att = ops.soa_attention(fgh, c)
         hw = x4.shape[1] * x4.shape[2]
-        if a.conv_math == "h2":
-            att_a = ops.amax_f32(att, ops.amax_records(1, dev)[0])
-            fgh_leg = lambda: ops.conv2d_h2(x4, x4a, blk.fgh_h2, blk.fgh_b, 1, 0, None, False)  # noqa: E731
-            v_leg = lambda: ops.conv2d_h2(att, att_a, blk.v_h2, blk.v_b, 1, 0, x4, False)  # noqa: E731
-        else:
-            fgh_leg = lambda: ops.conv2d(x4, blk.fgh_w, blk.fgh_b, 1, 0, None, False)  # noqa: E731
-            v_leg = lambda: ops.conv2d(att, blk.v_w, blk.v_b, 1, 0, x4, False)  # noqa: E731
+        att_a = ops.amax_of(att) if a.conv_math == "h2" else None
+        v_leg = lambda: blk.v(att, att_a, blk.v_b, residual=x4)  # noqa: E731
         net = alternated({"solar": lambda: solar.forward_test(x), "gem": lambda: gem.forward_test(x)}, a.rounds,
                          a.iters)
         head = alternated({"fgh conv": fgh_leg, "soa_attention": lambda: ops.soa_attention(fgh, c), "v conv": v_leg,

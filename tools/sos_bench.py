@@ -95,20 +95,20 @@ def main():
         gem = models.GeMWrapper(8, backbone="resnet50", seed=3, device=dev, conv_math=a.conv_math)
         net = models.SoSNetWrapper(8, backbone="resnet50", seed=3, device=dev, conv_math=a.conv_math)
         m = net.backbone
-        x4, x4a = m._trunk(xn)
+        x4, x4a = m.trunk_map(xn)
         t = alternated({"sos": lambda: net.forward_test(x), "gem": lambda: gem.forward_test(x),
                         "head": lambda: m.head(x4, x4a)}, a.rounds, a.iters)
         print(f"B={b} {h}x{w} R50 {a.conv_math}: SoSNetWrapper.forward_test {t['sos']:.3f} ms | "
               f"GeMWrapper.forward_test {t['gem']:.3f} ms | ratio {t['sos'] / t['gem']:.3f} | the head alone "
               f"(attention MLP, projection, rr_sos_cov, feature_proj) {t['head']:.3f} ms = "
               f"{100 * t['head'] / t['sos']:.1f} %", flush=True)
-        z = m._conv(x4, x4a, m.proj_w, m.proj_h2, None, False).view(b, 49, -1)
-        h1 = m._conv(x4, x4a, m.att_w1, m.att_h2, m.w["att_b1"], True)
+        z = m.proj(x4, x4a, None).view(b, 49, -1)
+        h1 = m.att1(x4, x4a, m.w["att_b1"], relu=True)
         hid = ops.linear_ex(h1.view(b * 49, -1), m.w["att_w2"], m.w["att_b2"], act=1).view(b, 49, -1)
         v, inv = ops.sos_cov(z, hid, m.w["att_w3"], m.att_b3)
         hd = ops.linear_splitk(v, m.w["fp0_w"], m.w["fp0_b"], row_scale=inv, act=1)
-        t = alternated({"att conv": lambda: m._conv(x4, x4a, m.att_w1, m.att_h2, m.w["att_b1"], True),
-                        "proj conv": lambda: m._conv(x4, x4a, m.proj_w, m.proj_h2, None, False),
+        t = alternated({"att conv": lambda: m.att1(x4, x4a, m.w["att_b1"], relu=True),
+                        "proj conv": lambda: m.proj(x4, x4a, None),
                         "linear_ex 512->256": lambda: ops.linear_ex(h1.view(b * 49, -1), m.w["att_w2"], m.w["att_b2"],
                                                                     act=1),
                         "sos_cov": lambda: ops.sos_cov(z, hid, m.w["att_w3"], m.att_b3),

@@ -71,9 +71,9 @@ def head_launches(m, b, hgt, wid, x4, x4a, a):
     r = ops.spp_regions(hgt, wid, LEVELS)
     w = m.w
     c1a = ops.amax_records(1, x4.device)[0] if m.conv_math == "h2" else None
-    c1 = m._conv(x4, x4a, "ce0_w", w["ce0_b"], 1, True, c1a)
-    ctx = m._conv(c1, c1a, "ce1_w", w["ce1_b"], 1, True)
-    u = m._conv(x4, x4a, "refine_wx", None, 0, False)
+    c1 = m.convs["ce0_w"](x4, x4a, w["ce0_b"], pad=1, relu=True, y_amax=c1a)
+    ctx = m.convs["ce1_w"](c1, c1a, w["ce1_b"], pad=1, relu=True)
+    u = m.convs["refine_wx"](x4, x4a, None)
     refined = ops.spoc_refine(u, ctx, w["att_w"], m.att_b, w["refine_wc"], w["refine_b"])
     pooled = ops.spp_max(refined, LEVELS)
     agg = ops.linear_groupmax(pooled, w["agg_w"], w["agg_b"], act=1)
@@ -83,11 +83,11 @@ def head_launches(m, b, hgt, wid, x4, x4a, a):
     def conv0():
         if c1a is not None:
             c1a.zero_()
-        return m._conv(x4, x4a, "ce0_w", w["ce0_b"], 1, True, c1a)
+        return m.convs["ce0_w"](x4, x4a, w["ce0_b"], pad=1, relu=True, y_amax=c1a)
 
     legs = {"conv3x3 2048->512": conv0,
-            "conv3x3 512->512": lambda: m._conv(c1, c1a, "ce1_w", w["ce1_b"], 1, True),
-            "conv1x1 Wx": lambda: m._conv(x4, x4a, "refine_wx", None, 0, False),
+            "conv3x3 512->512": lambda: m.convs["ce1_w"](c1, c1a, w["ce1_b"], pad=1, relu=True),
+            "conv1x1 Wx": lambda: m.convs["refine_wx"](x4, x4a, None),
             "spoc_refine": lambda: ops.spoc_refine(u, ctx, w["att_w"], m.att_b, w["refine_wc"], w["refine_b"]),
             "spp_max": lambda: ops.spp_max(refined, LEVELS),
             "linear_groupmax": lambda: ops.linear_groupmax(pooled, w["agg_w"], w["agg_b"], act=1),
@@ -162,7 +162,7 @@ def main():
         x = torch.randn((b, 3, h, w), device=dev, generator=g)
         xn = ops.nchw_to_nhwc(x, out_c=4)
         gem = models.GeMWrapper(8, backbone="resnet50", seed=3, device=dev, conv_math=a.conv_math)
-        x4, x4a = m._trunk(xn)
+        x4, x4a = m.trunk_map(xn)
         t = alternated({"spoc": lambda: net.forward_test(x), "gem": lambda: gem.forward_test(x),
                         "head": lambda: m.head(x4, x4a)}, a.rounds, max(1, a.iters // 4))
         print(f"B={b} {h}x{w} R50 {a.conv_math}: SpoCWrapper.forward_test {t['spoc'][0]:.3f} ms "

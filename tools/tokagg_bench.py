@@ -93,7 +93,7 @@ def main():
         x = torch.randn((b, 3, h, wd), device=dev, generator=g)
         xn = ops.nchw_to_nhwc(x, out_c=4)
         gem = models.GeMWrapper(8, backbone="resnet50", seed=3, device=dev, conv_math=a.conv_math)
-        x4, x4a = m._trunk(xn)
+        x4, x4a = m.trunk_map(xn)
         t = alternated({"token": lambda: net.forward_test(x), "gem": lambda: gem.forward_test(x),
                         "head": lambda: m.head(x4, x4a), "head unfolded": lambda: m.head(x4, x4a, fold_last=False)},
                        a.rounds, a.iters)

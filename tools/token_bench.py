@@ -86,10 +86,7 @@ def main():
     for b, h, w in ((64, 224, 224), (1, 768, 1024)):
         x = torch.randn((b, 3, h, w), device=dev, generator=g)
         xn = ops.nchw_to_nhwc(x, out_c=4)
-        if a.conv_math == "h2":
-            x4, x4a = tok.backbone(xn, return_amax=True)
-        else:
-            x4, x4a = tok.backbone(xn), None
+        _, x4, _, x4a = tok.backbone.maps(xn)
         n = x4.shape[1] * x4.shape[2]
         x4_nchw = x4.permute(0, 3, 1, 2).contiguous()
         net = alternated({"token": lambda: tok.forward_test(x), "gem": lambda: gem.forward_test(x)}, a.rounds, a.iters)
