@@ -79,10 +79,11 @@ typedef struct rr_handle_s* rr_handle_t;
  * trunk plan's rr_trunk_h2_* entries, rr_timing_collect_ex and the tuning key
  * RR_TUNE_TRUNK_PARTS (16); rr_timing_collect keeps its arguments and now
  * returns the UNION of the class's launch intervals (equal to the former sum
- * on one stream; see below).
+ * on one stream; see below); 8 = rr_h2_route was ADDED (which kernel
+ * instance serves an rr_conv2d_h2 shape; no existing entry changed).
  * Bindings compare rr_abi_version() with the RR_ABI_VERSION they were
  * written against.                                                          */
-#define RR_ABI_VERSION 7
+#define RR_ABI_VERSION 8
 int rr_abi_version(void);
 
 /* ---- handle ------------------------------------------------------------ */
@@ -131,7 +132,9 @@ int rr_get_device(rr_handle_t h, int* device);
  *                     4 (256x320 for bf16 filter / score sweeps, 256x256 otherwise),
  *                     5 (bf16 sweeps with K % 128 == 0, fp8 sweeps with K % 256 == 0:
  *                     256x256 8-phase pipeline; otherwise as 3)
- *   RR_TUNE_S3_CFG:   f16x2 split core, 1..15 (h2_tile.hip tile table; 13 = the halo-staged stride-1 3x3 tile on
+ *   RR_TUNE_S3_CFG:   f16x2 split core, 1..15 (the table of csrc/h2_route.hpp; rr_h2_route
+ *                     reports what a value selects; 1, 2, 5 and 6 are accepted and mean the
+ *                     library's pick among the one-tile configs 3, 4 and 7; 13 = the halo-staged stride-1 3x3 tile on
  *                     v_mfma_f32_32x32x16_f16, 14 = the same on v_mfma_f32_16x16x32_f16
  *                     (the default picks 14's form for cout % 256 == 0, 13's for cout 64);
  *                     15 = the 256x256 tile (12) as a persistent k-stream (the default
@@ -400,6 +403,36 @@ int rr_conv2d_h2(rr_handle_t h, const float* x, const unsigned* x_amax, int b,
                  const float* w_iscale, const float* bias, int cout, int kh,
                  int kw, int stride, int pad, const float* residual, int relu,
                  float* y, unsigned* y_amax, void* stream);
+
+/* Which kernel instance rr_conv2d_h2 runs for a shape under given tuning
+ * values, and how it is launched (ABI 8).  Host only, no handle, no GPU: the
+ * same geometry and the same route function (csrc/h2_route.hpp) as the call
+ * itself.  RR_EINVAL for a shape rr_conv2d_h2 rejects or a tuning value
+ * rr_set_tuning rejects (b == 0, which launches nothing, reports the route
+ * of its shape).
+ * family: 0 one tile per block (h2_tile.hip), 1 the config-8 k-stream, 2 the
+ * config-15 256-row k-stream, 3 the raster halo tile, 4 the 2-D halo tile.
+ * cfg: the tile table's number (3, 4, 7 to 15; 13 / 14 = a halo tile on
+ * 32x32x16 / 16x16x32).  wm .. t2: the kernel template's tuple, 0 where the
+ * family has no such parameter: wm x wn waves of fm x fn 32x32 MFMA tiles,
+ * k-tile depth bk, halo buffer rows hr, taps per barrier tpk, mf16 (1 =
+ * v_mfma_f32_16x16x32_f16), LDS stages nstg, accumulator sets acc, il (loads
+ * spread among the MFMAs), pers (1 = persistent stream; halo tiles 2 = one
+ * halo buffer at 256 rows), t2 (2-D halo tile: output columns).  chunk_rows:
+ * rows per launch where x or y has 4 GB or more, 0 = one launch.           */
+typedef struct {
+  int b, h, w, cin, cout, kh, kw, stride, pad;
+  int residual, relu; /* 0 / 1 */
+} rr_h2_shape_t;
+typedef struct {
+  int s3_cfg, s3_cfg_res, halo_mf, halo_2d, conv_il; /* as rr_set_tuning's keys */
+} rr_h2_tune_t;
+typedef struct {
+  int family, cfg;
+  int wm, wn, fm, fn, bk, hr, tpk, mf16, nstg, acc, il, pers, t2;
+  long long chunk_rows;
+} rr_h2_route_t;
+int rr_h2_route(const rr_h2_shape_t* shape, const rr_h2_tune_t* tune, rr_h2_route_t* out);
 
 /* The output of a stage-entry bottleneck block on the f16x2 core, its 1x1
  * conv3 and its 1x1 strided downsample projection as ONE GEMM over

@@ -19,13 +19,10 @@
 // 256x256 tile, 8 waves of 128x64 on v_mfma_f32_32x32x16_f16, one accumulator
 // set (ACC1, config 12's arithmetic per product); the next slice's halo goes
 // to the other buffer one 128-row pass per k-tile during the slice's first
-// four.  Instances (waves WM x WN of FM x FN 32x32 tiles, halo rows HR):
-//   <2, 4, 4, 2, 288>  256x256, N % 256 == 0, W <= 15 (the 14x14 / 7x7 layers)
-//   <4, 2, 2, 2, 320>  256x128, N % 128 == 0, W <= 31 (28x28, N = 128)
-//   <4, 2, 2, 1, 384>  256x64,  N % 64 == 0,  W <= 63 (56x56, N = 64), three
-//                      taps per k-step (and barrier): its 12 MFMAs per wave
-//                      and tap are too few to carry a barrier each
-// Row HR of each halo plane is the zero row.
+// four.  Instances (waves WM x WN of FM x FN 32x32 tiles, halo rows HR): the
+// table RR_H2_HALO_INSTANCES in h2_route.hpp; the 256x64 tile takes three taps
+// per k-step (and barrier): its 12 MFMAs per wave and tap are too few to
+// carry a barrier each.  Row HR of each halo plane is the zero row.
 // Halo rows are read 32 at a time from any row offset r0 + kh W + kw, not from
 // 32-aligned groups, so the row-group swizzle of the other tiles (pswz<32>)
 // conflicts there (PMC: 3.5e7 SQ_LDS_BANK_CONFLICT on the 3x3 256@14 layer,
@@ -36,6 +33,7 @@
 #include <algorithm>
 
 #include "h2_common.hpp"
+#include "h2_route.hpp"
 
 namespace rr {
 
@@ -567,20 +565,6 @@ __global__ __launch_bounds__(512, 1) void gemm_h2_halo_kernel(GemmArgs g, int ti
   RR_PH_FLUSH();
 }
 
-// config 13 serves: f16x2, conv A, 3x3 stride 1 pad 1 (output = input size),
-// Cin % 32 == 0, N % 64 == 0 and W within the instance's halo (see above),
-// the ResNet's f16x2 flag sets.  Returns the halo rows of the instance that
-// serves g, 0 if none.
-int h2_halo_rows(const GemmArgs& g) {
-  if (!(g.KH == 3 && g.KW == 3 && g.stride == 1 && g.pad == 1 && g.OH == g.H && g.OW == g.W && (g.Cin % 32) == 0 &&
-        g.K == 9 * g.Cin && g.col_scale != nullptr && g.a_amax != nullptr))
-    return 0;
-  const int need = 256 + 2 * (g.W + 1);
-  if ((g.N % 256) == 0) return need <= 288 ? 288 : 0;
-  if ((g.N % 128) == 0) return need <= 320 ? 320 : 0;
-  if ((g.N % 64) == 0) return need <= 384 ? 384 : 0;
-  return 0;
-}
 template <int EPI, int WM, int WN, int FM, int FN, int HR, int TPK, int MF, int IL = 0, int PERS = 0, int T2 = 0>
 static hipError_t launch_h2_halo_t(const GemmArgs& g, hipStream_t s, int n_cu = 256) {
   constexpr int BN = 32 * FN * WN, BM = 32 * FM * WM;
@@ -599,73 +583,31 @@ static hipError_t launch_h2_halo_t(const GemmArgs& g, hipStream_t s, int n_cu = 
                      0, s, g, (int)tiles_n);
   return hipGetLastError();
 }
-template <int WM, int WN, int FM, int FN, int HR, int TPK, int MF, int IL = 0, int PERS = 0>
-static hipError_t launch_h2_halo_ep(const GemmArgs& g, hipStream_t s, int n_cu = 256) {
-  return h2_ep_dispatch<false>(g, [&](auto ep) {
-    return launch_h2_halo_t<decltype(ep)::value, WM, WN, FM, FN, HR, TPK, MF, IL, PERS>(g, s, n_cu);
-  });
-}
-// mf: 1 = the 16x16x32 form (s3_cfg 14 forces it); pers: the N = 64 instance
-// as a persistent stream (one column tile)
-hipError_t launch_h2_halo(const GemmArgs& g, hipStream_t s, int hr, int mf, bool pers, int n_cu) {
-  // N = 64 (the 64@56 layers): the 512-row single-buffer tile, 8 waves of
-  // 64 x 64, wherever its 640-row halo holds the map (W <= 63): every wave
-  // reads 64 + 64 fragment rows per tap for 24 MFMAs instead of 64 + 32 for
-  // 12, and the taps of a barrier carry 72 MFMAs per wave instead of 36.
-  // 1.193 -> 1.059 ms at 1280 images, bit-identical
-  // (profiles/r06r_halo512_ab.txt).  halo_mf 3 forces the persistent
-  // 256-row stream (round 5's default), 2 the 512-row tile.
-  if (hr == 384 && g.N == 64 && (mf == 2 || (mf == 0 && pers)) && 512 + 2 * (g.W + 1) <= 640)
-    return launch_h2_halo_ep<8, 1, 2, 2, 640, 3, 0>(g, s);
-  // N = 128 on 16x16x32: one halo buffer and three taps per barrier (the
-  // LDS the second halo buffer held now holds three taps' B stages): 0.924 ->
-  // 0.897 ms at 128@28, bit-identical (profiles/r06z2_halo128_sb_ab.txt);
-  // halo_mf 4 keeps the two-buffer one-tap form for A/Bs
-  if (hr == 320 && mf == 4) return launch_h2_halo_ep<4, 2, 2, 2, 320, 1, 1>(g, s);
-  if (hr == 320 && mf == 1) return launch_h2_halo_ep<4, 2, 2, 2, 320, 3, 1, 0, 2>(g, s);
-  if (mf >= 2) {
-    pers = pers || mf == 3;
-    mf = mf == 4 ? 1 : 0;
+// The raster instances with the four residual / ReLU epilogues; the 2-D block
+// tiles (T2: maps too wide for a raster halo, C2's 1024-px layers 1-3) with
+// the two that have no residual (the trunk's 3x3s have none).
+template <int WM, int WN, int FM, int FN, int HR, int TPK, int MF, int IL, int PERS, int T2>
+static hipError_t launch_h2_halo_i(const GemmArgs& g, hipStream_t s, int n_cu) {
+  if constexpr (T2 != 0) {
+    if ((ep_flags(g) & EP_RES) != 0) return hipErrorInvalidValue;
+    if ((ep_flags(g) & EP_RELU) != 0)
+      return launch_h2_halo_t<H2_EP | EP_RELU, WM, WN, FM, FN, HR, TPK, MF, 0, PERS, T2>(g, s);
+    return launch_h2_halo_t<H2_EP, WM, WN, FM, FN, HR, TPK, MF, 0, PERS, T2>(g, s);
+  } else {
+    return h2_ep_dispatch<false>(g, [&](auto ep) {
+      return launch_h2_halo_t<decltype(ep)::value, WM, WN, FM, FN, HR, TPK, MF, IL, PERS>(g, s, n_cu);
+    });
   }
-  if (hr == 384 && !mf && pers && g.N == 64) return launch_h2_halo_ep<4, 2, 2, 1, 384, 3, 0, 0, 1>(g, s, n_cu);
-  // (the 16x16x32 256x256 form with its B DMA spread among the MFMAs: conv_il)
-  if (hr == 288 && mf && g.issue_spread) return launch_h2_halo_ep<2, 4, 4, 2, 288, 1, 1, 1>(g, s);
-  if (hr == 288) return mf ? launch_h2_halo_ep<2, 4, 4, 2, 288, 1, 1>(g, s) : launch_h2_halo_ep<2, 4, 4, 2, 288, 1, 0>(g, s);
-  if (hr == 320) return mf ? launch_h2_halo_ep<4, 2, 2, 2, 320, 1, 1>(g, s) : launch_h2_halo_ep<4, 2, 2, 2, 320, 1, 0>(g, s);
-  return mf ? launch_h2_halo_ep<4, 2, 2, 1, 384, 3, 1>(g, s) : launch_h2_halo_ep<4, 2, 2, 1, 384, 3, 0>(g, s);
 }
-
-// The 2-D block tiles (T2) for the stride-1 3x3 layers of maps too wide for a
-// raster halo (C2's 1024-px layers 1-3: W 256 / 128 / 64): the tile's halo is
-// (TH + 2)(T2 + 2) rows whatever W is.  Instances: 16 x 16 outputs, 18 x 18 =
-// 324 halo rows, on the 256x256 (N % 256) and 256x128 single-buffer three-tap
-// (N = 128) tiles; 16 x 32 outputs, 18 x 34 = 612 rows, on the 512-row N = 64
-// tile.  No residual epilogue (the trunk's 3x3s have none).  Returns whether
-// one serves g.
-bool h2_halo_2d_ok(const GemmArgs& g) {
-  if (!(g.KH == 3 && g.KW == 3 && g.stride == 1 && g.pad == 1 && g.OH == g.H && g.OW == g.W && (g.Cin % 32) == 0 &&
-        g.K == 9 * g.Cin && g.col_scale != nullptr && g.a_amax != nullptr && g.H > 0 && g.W > 0 &&
-        (g.M % (g.H * g.W)) == 0 && (ep_flags(g) & EP_RES) == 0))
-    return false;
-  if (g.N == 128) {
-    // the N = 128 tile needs a block per CU: below that config 11's
-    // 128-column tiles spread further (a batch-1 128@75x100 crop, 35 blocks:
-    // 0.040 -> 0.045 ms; 64 images of 128@128x96: 0.811 -> 0.685 ms;
-    // profiles/r06zb_halo2d_ab.txt)
-    const long long blocks = (long long)(g.M / (g.H * g.W)) * ((g.H + 15) / 16) * ((g.W + 15) / 16);
-    return blocks >= 256 || g.halo_2d == 1;
-  }
-  return (g.N % 256) == 0 || g.N == 64;
-}
-template <int WM, int WN, int FM, int FN, int HR, int TPK, int MF, int PERS, int T2>
-static hipError_t launch_h2_halo_2d_ep(const GemmArgs& g, hipStream_t s) {
-  if ((ep_flags(g) & EP_RELU) != 0) return launch_h2_halo_t<H2_EP | EP_RELU, WM, WN, FM, FN, HR, TPK, MF, 0, PERS, T2>(g, s);
-  return launch_h2_halo_t<H2_EP, WM, WN, FM, FN, HR, TPK, MF, 0, PERS, T2>(g, s);
-}
-hipError_t launch_h2_halo_2d(const GemmArgs& g, hipStream_t s) {
-  if (g.N == 64) return launch_h2_halo_2d_ep<8, 1, 2, 2, 640, 3, 0, 0, 32>(g, s);
-  if (g.N == 128) return launch_h2_halo_2d_ep<4, 2, 2, 2, 324, 3, 1, 2, 16>(g, s);
-  return launch_h2_halo_2d_ep<2, 4, 4, 2, 324, 1, 1, 0, 16>(g, s);
+// the route's tuple -> the instance (the table: h2_route.hpp)
+hipError_t launch_h2_halo(const H2Route& r, const GemmArgs& g, hipStream_t s, int n_cu) {
+#define RR_X(WM, WN, FM, FN, HR, TPK, MF, IL, PERS, T2)                                                             \
+  if (r.wm == WM && r.wn == WN && r.fm == FM && r.fn == FN && r.hr == HR && r.tpk == TPK && r.mf16 == MF && r.il == IL && \
+      r.pers == PERS && r.t2 == T2)                                                                                 \
+    return launch_h2_halo_i<WM, WN, FM, FN, HR, TPK, MF, IL, PERS, T2>(g, s, n_cu);
+  RR_H2_HALO_INSTANCES(RR_X)
+#undef RR_X
+  return hipErrorInvalidValue;
 }
 
 #if RR_S3_PHASES

@@ -403,7 +403,7 @@ static hipError_t launch_s3p_t(GemmArgs g, hipStream_t s, int n_cu, int stagger)
   return hipGetLastError();
 }
 
-// config 8: dense A, N % 256 == 0 (s3_persist_ok, h2_dispatch.hip)
+// config 8: dense A, N % 256 == 0 (s3_persist_ok, h2_route.hpp)
 hipError_t launch_s3p(const GemmArgs& g, hipStream_t s, int n_cu, int st) {
   // residual epilogues streamed (EP_SC1, as config 15's): 128->512 + residual
   // x3 0.908 -> 0.877 ms, 64->256 x2 1.701 -> 1.707; the embed 69.09 -> 69.06

@@ -30,6 +30,7 @@
 #include <algorithm>
 
 #include "h2_common.hpp"
+#include "h2_route.hpp"
 
 namespace rr {
 
@@ -377,17 +378,6 @@ __global__ __launch_bounds__(512, 1) void gemm_s3q_kernel(GemmArgs g, int tiles_
   }
 }
 
-// config 15 serves dense A at N % 256 == 0 or N == 128 with K >= 256 (the
-// 256x256 and 256x128 forms), and N == 64 with K >= 64 (the 256x64 form)
-bool s3q_shape(const GemmArgs& g) {
-  return ((g.N % 256) == 0 && g.K >= 256) || (g.N == 128 && g.K >= 256) || (g.N == 64 && g.K >= 64);
-}
-// config 15 addresses A and the residual by 32-bit byte offsets
-bool s3q_fits(const GemmArgs& g) {
-  const long long lim = 1LL << 32;
-  return (long long)g.M * g.lda * 4 < lim && (long long)g.M * g.ldc * 4 < lim;
-}
-
 template <int EPI, int FN = 2, int WM = 2, int ACC2 = 0>
 static hipError_t launch_s3q_t(GemmArgs g, hipStream_t s, int n_cu, int stagger) {
   const long long tiles_m = (g.M + 255) / 256, tiles_n = g.N / (32 * FN * (8 / WM));
@@ -402,8 +392,8 @@ static hipError_t launch_s3q_t(GemmArgs g, hipStream_t s, int n_cu, int stagger)
   hipLaunchKernelGGL((gemm_s3q_kernel<EPI, FN, WM, ACC2>), dim3((unsigned)grid), dim3(512), 0, s, g, (int)tiles_n, (int)ntiles);
   return hipGetLastError();
 }
-// the form that serves g's N (s3q_shape; the caller checks s3q_fits too)
-hipError_t launch_s3q(const GemmArgs& g, hipStream_t s, int n_cu, int st) {
+// the route's form (h2_stream256_route; s3q_shape and s3q_fits hold for g)
+hipError_t launch_s3q(const H2Route& r, const GemmArgs& g, hipStream_t s, int n_cu, int st) {
   // residual epilogues streamed (EP_SC1): output stores sc1, residual
   // loads nt -- neither keeps XCD L2 lines the row tile's other column
   // tiles still re-read (256->1024 + residual 0.604 -> 0.579 ms, 512->2048
@@ -413,9 +403,10 @@ hipError_t launch_s3q(const GemmArgs& g, hipStream_t s, int n_cu, int st) {
   // r05j_probe2.txt)
   return h2_ep_dispatch<true>(g, [&](auto ep) {
     constexpr int EPI = decltype(ep)::value;
-    if (g.N == 64) return launch_s3q_t<EPI, 1, 4, 1>(g, s, n_cu, st);
-    if (g.N == 128) return launch_s3q_t<EPI, 1>(g, s, n_cu, st);
-    return launch_s3q_t<EPI>(g, s, n_cu, st);
+    if (r.wm == 4 && r.fn == 1 && r.acc == 2) return launch_s3q_t<EPI, 1, 4, 1>(g, s, n_cu, st);
+    if (r.wm == 2 && r.fn == 1 && r.acc == 1) return launch_s3q_t<EPI, 1>(g, s, n_cu, st);
+    if (r.wm == 2 && r.fn == 2 && r.acc == 1) return launch_s3q_t<EPI>(g, s, n_cu, st);
+    return hipErrorInvalidValue;
   });
 }
 

@@ -18,10 +18,11 @@
 // copied global -> LDS by LDS-DMA (global_load_lds).  16-B slots of the LDS
 // rows are XOR-swizzled so the fragment ds_read_b128 are conflict-free.
 // The other kernels of the family: h2_stream.hip (config 8), h2_stream256.hip
-// (15), h2_halo.hip (13 / 14), h2_stem.hip; h2_dispatch.hip picks among them.
+// (15), h2_halo.hip (13 / 14), h2_stem.hip; h2_route.hpp picks among them.
 #include <algorithm>
 
 #include "h2_common.hpp"
+#include "h2_route.hpp"
 
 namespace rr {
 
@@ -643,47 +644,23 @@ static hipError_t launch_s3_t(GemmArgs g, hipStream_t s, int n_cu, int stagger) 
 }
 
 // Tile configs (waves WMxWN, MFMA tiles per wave FMxFN, BK, blocks per CU,
-// LDS of the two stages).  Configs 1, 2, 5 and 6 have no instance: they stay
-// in the table because the pick's cost model and the tuning key still name
-// them (a forced 1, 2, 5 or 6 runs the pick).
-//   1: 128x128, 4 waves of 64x64, BK 16, 2/CU
-//   2: 128x128, 4 waves of 64x64, BK 32, 1/CU
+// LDS of the two stages).  Which one serves a GEMM, and the measurements
+// behind that: h2_route.hpp.
 //   3: 256x128, 8 waves of 64x64, BK 32, 1/CU (96 KB)
 //   4: 128x256, 8 waves of 64x64, BK 32, 1/CU (96 KB), v_mfma_f32_16x16x32_f16
-//   5: 256x64,  4 waves of 64x64, BK 32, 1/CU
-//   6: 256x64,  4 waves of 64x64, BK 16, 2/CU
 //   7: 256x64,  8 waves of 32x64, BK 16, 2/CU (40 KB), 4 waves per SIMD
-//      (<= 128 registers): the picked 256x64 tile (the N = 64 layers and the
-//      stem 2-7 % faster than 6, profiles/r02f_s3_cfg7.txt; dense N = 64
-//      now takes config 15's 256x64 form, profiles/r05ah_s3q64_ab/)
-//   8: config 4 as a persistent k-stream (gemm_s3p_kernel): dense A, N % 256
-//      == 0 — the picked tile for the 1x1 layers it serves
 //   9: config 4 with three LDS stages (144 KB): the B DMA two k-tiles ahead
 //  10: config 4 with one accumulator set (ACC1: the plane-1 products
 //      accumulate with a0b0; error vs float64 still at the exact-fp32
 //      core's, profiles/r03j_acc1_ab.txt; 196 instead of 254 VGPRs)
-//  11: 128x128, 4 waves of 64x64, BK 32, 2/CU (64 KB), 16x16x32, ACC1: the
-//      picked tile for N == 128 (dense K >= 256: config 15's 256x128 form)
+//  11: 128x128, 4 waves of 64x64, BK 32, 2/CU (64 KB), 16x16x32, ACC1
 //  12: 256x256, 8 waves of 128x64, BK 32, 1/CU (128 KB), 32x32x16, ACC1
-//      (254 VGPRs — two accumulator sets do not fit this tile): half the
-//      operand bytes per FLOP of config 4, the picked tile for N % 256 == 0
-//      except the K < 256 residual expansions
-//  15: config 12 as a persistent k-stream (gemm_s3q_kernel, dense A,
-//      config 12's shapes; the pick there): the next tile's first k-tiles load under
-//      the epilogue, which runs in four slabs with the residual two 32-row
-//      bands ahead; bit-identical to config 12.  Its 256x128 form serves
-//      dense N == 128, K >= 256, its 256x64 form dense N == 64, K >= 64
-// (all others on v_mfma_f32_32x32x16_f16).  Instances: 3, 4, 7 and 9 to 12
-// here (launch_h2_tile_am), 8 in h2_stream.hip, 15 in h2_stream256.hip, 13 /
-// 14 (the halo tile) in h2_halo.hip; the pick is in h2_dispatch.hip.
-// Measured per R101 layer at 320 images (round 2's tools/s3_bench.py): 3 is the fastest
-// wherever N >= 128 (1.1-1.3x config 1 per FLOP); 4 on 16x16x32 runs every
-// N % 256 == 0 layer 3-14 % faster than 3 (the 16x16 shape holds a higher
-// clock on random operands, MI355X_MICROARCH.md 'DVFS give-back' item 7; the
-// same shape is slower in the one-wave-per-SIMD configs 2 and 5 and spills in
-// 3).  Not kept: an all-DMA ring with the A split at fragment-read
-// time (10-15 % slower), a one-wave-per-SIMD 256x128 variant (1.16x slower).
-// rr_set_tuning(RR_TUNE_S3_CFG) forces a config (tests, tools).
+//      (254 VGPRs -- two accumulator sets do not fit this tile): half the
+//      operand bytes per FLOP of config 4
+// (8 and 15: configs 4 and 12 as persistent k-streams, h2_stream.hip and
+// h2_stream256.hip, bit-identical to them; 13 / 14: the halo tiles,
+// h2_halo.hip).  The 16x16 shape holds a higher clock on random operands
+// (MI355X_MICROARCH.md 'DVFS give-back' item 7); it spills in config 3's tile.
 
 // The tile configs with the ResNet's epilogues compiled in: the four residual
 // / ReLU combinations of H2_EP (conv + BN + ReLU, + residual + ReLU,
@@ -695,27 +672,24 @@ static hipError_t launch_s3_ep(const GemmArgs& g, hipStream_t s, int n_cu, int s
   });
 }
 
+// the route's tuple -> the instance (the table: h2_route.hpp)
 template <int AM>
-static hipError_t launch_h2_tile_am(int cfg, const GemmArgs& g, hipStream_t s, int n_cu, int st) {
-  switch (cfg) {
-    case 4: return launch_s3_ep<2, 4, 2, 2, 32, AM, 1, 1>(g, s, n_cu, st);
-    case 9: return launch_s3_ep<2, 4, 2, 2, 32, AM, 1, 1, 3>(g, s, n_cu, st);
-    case 10: return launch_s3_ep<2, 4, 2, 2, 32, AM, 1, 1, 2, 1>(g, s, n_cu, st);
-    case 11: return launch_s3_ep<2, 2, 2, 2, 32, AM, 2, 1, 2, 1>(g, s, n_cu, st);
-    case 12:
-      if constexpr (AM != A_CONV_C4) {
-        if (g.issue_spread) return launch_s3_ep<2, 4, 4, 2, 32, AM, 1, 0, 2, 1, 1>(g, s, n_cu, st);
-      }
-      return launch_s3_ep<2, 4, 4, 2, 32, AM, 1, 0, 2, 1>(g, s, n_cu, st);
-    case 7: return launch_s3_ep<8, 1, 1, 2, 16, AM, 4, 0>(g, s, n_cu, st);
-    default: return launch_s3_ep<4, 2, 2, 2, 32, AM, 1, 0>(g, s, n_cu, st);
+static hipError_t launch_h2_tile_am(const H2Route& r, const GemmArgs& g, hipStream_t s, int n_cu, int st) {
+#define RR_X(CFG, WM, WN, FM, FN, BK, MINB, MF16, NSTG, ACC1, IL)                                                       \
+  if constexpr (!(IL && AM == A_CONV_C4)) {                                                                             \
+    if (r.cfg == CFG && r.wm == WM && r.wn == WN && r.fm == FM && r.fn == FN && r.bk == BK && r.mf16 == MF16 &&        \
+        r.nstg == NSTG && r.acc == (ACC1 ? 1 : 2) && r.il == IL)                                                        \
+      return launch_s3_ep<WM, WN, FM, FN, BK, AM, MINB, MF16, NSTG, ACC1, IL>(g, s, n_cu, st);                          \
   }
+  RR_H2_TILE_INSTANCES(RR_X)
+#undef RR_X
+  return hipErrorInvalidValue;
 }
 
-hipError_t launch_h2_tile(int cfg, int amode, const GemmArgs& g, hipStream_t s, int n_cu, int st) {
-  return amode == A_DENSE  ? launch_h2_tile_am<A_DENSE>(cfg, g, s, n_cu, st)
-         : amode == A_CONV ? launch_h2_tile_am<A_CONV>(cfg, g, s, n_cu, st)
-                           : launch_h2_tile_am<A_CONV_C4>(cfg, g, s, n_cu, st);
+hipError_t launch_h2_tile(const H2Route& r, int amode, const GemmArgs& g, hipStream_t s, int n_cu, int st) {
+  return amode == A_DENSE  ? launch_h2_tile_am<A_DENSE>(r, g, s, n_cu, st)
+         : amode == A_CONV ? launch_h2_tile_am<A_CONV>(r, g, s, n_cu, st)
+                           : launch_h2_tile_am<A_CONV_C4>(r, g, s, n_cu, st);
 }
 
 // the implicit-GEMM stem + max-pool (config 7 on NHWC4 with POOL; q.M = 256 rows per tile)

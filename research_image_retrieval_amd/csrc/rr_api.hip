@@ -4,6 +4,7 @@
 #include <initializer_list>
 
 #include "gemm_epilogue.hpp"
+#include "h2_route.hpp"
 #include "rr_internal.hpp"
 
 namespace rr {
@@ -519,26 +520,19 @@ int rr_conv2d(rr_handle_t h, const float* x, int b, int hgt, int wid, int cin, c
   return launch_gemm(h, amode, E_STORE, g, (hipStream_t)stream, kTimeGemm);
 }
 
-int rr_conv2d_h2(rr_handle_t h, const float* x, const unsigned* x_amax, int b, int hgt, int wid, int cin,
-                 const void* w2, const float* w_iscale, const float* bias, int cout, int kh, int kw, int stride,
-                 int pad, const float* residual, int relu, float* y, unsigned* y_amax, void* stream) {
-  RR_ENTRY(h);
-  if (!x || !x_amax || !w2 || !w_iscale || !y || b < 0 || hgt <= 0 || wid <= 0 || cin <= 0 || cout <= 0 ||
-      kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || relu < 0 || relu > 1)
-    return set_error(h, RR_EINVAL, "rr_conv2d_h2: bad argument");
-  if (cin % 32 && cin != 4) return set_error(h, RR_EINVAL, "rr_conv2d_h2: cin must be a multiple of 32, or 4 (NHWC4 stem)");
-  if (cout % 4) return set_error(h, RR_EINVAL, "rr_conv2d_h2: cout must be a multiple of 4");
+// rr_conv2d_h2's GEMM: the shape checks and the geometry (no pointer), shared
+// with rr_h2_route.  Returns what is wrong with the shape, nullptr if nothing.
+static const char* conv2d_h2_geometry(int b, int hgt, int wid, int cin, int cout, int kh, int kw, int stride, int pad,
+                                      int relu, GemmArgs& g, int& amode) {
+  if (b < 0 || hgt <= 0 || wid <= 0 || cin <= 0 || cout <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || relu < 0 ||
+      relu > 1)
+    return "rr_conv2d_h2: bad argument";
+  if (cin % 32 && cin != 4) return "rr_conv2d_h2: cin must be a multiple of 32, or 4 (NHWC4 stem)";
+  if (cout % 4) return "rr_conv2d_h2: cout must be a multiple of 4";
   const int oh = (hgt + 2 * pad - kh) / stride + 1, ow = (wid + 2 * pad - kw) / stride + 1;
-  if (oh <= 0 || ow <= 0) return set_error(h, RR_EINVAL, "rr_conv2d_h2: empty output");
+  if (oh <= 0 || ow <= 0) return "rr_conv2d_h2: empty output";
   const long long M = (long long)b * oh * ow;
-  if (M > 0x7fffffffLL) return set_error(h, RR_EINVAL, "rr_conv2d_h2: too many output pixels");
-  // the epilogues load bias / col_scale as f32x4 and store C / read the
-  // residual in 16-byte pieces
-  if (((uintptr_t)x & 15) || ((uintptr_t)w2 & 15) || ((uintptr_t)w_iscale & 15) || ((uintptr_t)y & 15) ||
-      (bias && ((uintptr_t)bias & 15)) || (residual && ((uintptr_t)residual & 15)))
-    return set_error(h, RR_EINVAL, "rr_conv2d_h2: x/w2/w_iscale/bias/residual/y must be 16-byte aligned");
-  GemmArgs g;
-  g.A = x;
+  if (M > 0x7fffffffLL) return "rr_conv2d_h2: too many output pixels";
   g.M = (int)M;
   g.K = kh * kw * cin;
   g.H = hgt;
@@ -551,21 +545,63 @@ int rr_conv2d_h2(rr_handle_t h, const float* x, const unsigned* x_amax, int b, i
   g.stride = stride;
   g.pad = pad;
   if (cin == 4) g.K = (g.K + 31) / 32 * 32;  // NHWC4 stem: planes zero-padded to a multiple of 32
-  g.B = reinterpret_cast<const float*>(w2);
   g.ldb = g.K;
   g.b_plane = (long long)cout * g.K;
   g.N = cout;
-  g.C = y;
   g.ldc = cout;
+  g.relu = relu;
+  const bool dense = kh == 1 && kw == 1 && stride == 1 && pad == 0 && cin != 4;
+  if (dense) g.lda = cin;
+  amode = dense ? A_DENSE : (cin == 4 ? A_CONV_C4 : A_CONV);
+  return nullptr;
+}
+
+int rr_conv2d_h2(rr_handle_t h, const float* x, const unsigned* x_amax, int b, int hgt, int wid, int cin,
+                 const void* w2, const float* w_iscale, const float* bias, int cout, int kh, int kw, int stride,
+                 int pad, const float* residual, int relu, float* y, unsigned* y_amax, void* stream) {
+  RR_ENTRY(h);
+  if (!x || !x_amax || !w2 || !w_iscale || !y) return set_error(h, RR_EINVAL, "rr_conv2d_h2: bad argument");
+  GemmArgs g;
+  int amode;
+  if (const char* err = conv2d_h2_geometry(b, hgt, wid, cin, cout, kh, kw, stride, pad, relu, g, amode))
+    return set_error(h, RR_EINVAL, err);
+  // the epilogues load bias / col_scale as f32x4 and store C / read the
+  // residual in 16-byte pieces
+  if (((uintptr_t)x & 15) || ((uintptr_t)w2 & 15) || ((uintptr_t)w_iscale & 15) || ((uintptr_t)y & 15) ||
+      (bias && ((uintptr_t)bias & 15)) || (residual && ((uintptr_t)residual & 15)))
+    return set_error(h, RR_EINVAL, "rr_conv2d_h2: x/w2/w_iscale/bias/residual/y must be 16-byte aligned");
+  g.A = x;
+  g.B = reinterpret_cast<const float*>(w2);
+  g.C = y;
   g.bias = bias;
   g.residual = residual;
-  g.relu = relu;
   g.col_scale = w_iscale;
   g.a_amax = x_amax;
   g.c_amax = y_amax;
-  const bool dense = kh == 1 && kw == 1 && stride == 1 && pad == 0 && cin != 4;
-  if (dense) g.lda = cin;
-  return launch_gemm_s3(h, dense ? A_DENSE : (cin == 4 ? A_CONV_C4 : A_CONV), g, (hipStream_t)stream, kTimeGemm);
+  return launch_gemm_s3(h, amode, g, (hipStream_t)stream, kTimeGemm);
+}
+
+int rr_h2_route(const rr_h2_shape_t* sh, const rr_h2_tune_t* tu, rr_h2_route_t* out) {
+  if (!sh || !tu || !out || (sh->residual & ~1)) return RR_EINVAL;
+  if (tu->s3_cfg < 0 || tu->s3_cfg > 15 || tu->s3_cfg_res < 0 || tu->s3_cfg_res > 15 || tu->halo_mf < -1 ||
+      tu->halo_mf > 4 || tu->halo_2d < -1 || tu->halo_2d > 1 || tu->conv_il < -1 || tu->conv_il > 1)
+    return RR_EINVAL;
+  GemmArgs g;
+  int amode;
+  if (conv2d_h2_geometry(sh->b, sh->h, sh->w, sh->cin, sh->cout, sh->kh, sh->kw, sh->stride, sh->pad, sh->relu, g, amode))
+    return RR_EINVAL;
+  if (h2_shape_error(amode, g)) return RR_EINVAL;
+  static const float a_residual = 0.f;  // (the route only asks whether there is one)
+  if (sh->residual) g.residual = &a_residual;
+  rr_handle_s::Tuning t;
+  t.s3_cfg = tu->s3_cfg;
+  t.s3_cfg_res = tu->s3_cfg_res;
+  t.halo_mf = tu->halo_mf;
+  t.halo_2d = tu->halo_2d;
+  t.conv_il = tu->conv_il;
+  const H2Route r = h2_route(amode, g, h2_tune(t, sh->residual != 0));
+  *out = {r.family, r.cfg, r.wm, r.wn, r.fm, r.fn, r.bk, r.hr, r.tpk, r.mf16, r.nstg, r.acc, r.il, r.pers, r.t2, r.chunk_rows};
+  return RR_OK;
 }
 
 int rr_stem_pool_h2(rr_handle_t h, const float* x, const unsigned* x_amax, int b, int hgt, int wid, const void* w2,

@@ -22,7 +22,7 @@ struct rr_handle_s {
     int gemm_cfg = 0;  // fp32 core: 22, 41 or 88
     int gemm_bk = 0;   // fp32 core k-tile depth: 16 or 32
     int lp_cfg = 0;    // bf16 / fp8 core: 1 = 128x128, 2 = 256x64, 3 = 256x256, 4 = 256x320 (filter sweeps), 5 = 8-phase 256x256 (bf16 / fp8 sweeps), 6 = the persistent bf16 tile with three A stages (tests); 0: the pick (the persistent 256x256 bf16 tile for the ViT epilogues, K <= 1024)
-    int s3_cfg = 0;    // f16x2 split core: 1..15 (h2_tile.hip tile table); 0: the pick
+    int s3_cfg = 0;    // f16x2 split core: 1..15 (h2_route.hpp's table); 0: the pick
     int s3_stagger = -1;  // f16x2 split core round stagger in ~1 us sleeps (-1: the library's pick)
     int sweep_mf16 = -1;   // bf16 256x320 filter sweep on v_mfma_f32_16x16x32_bf16 (1) or 32x32x16 (0); -1: the pick (0)
     int sweep_il = -1;     // bf16 256x320 filter sweep: next k-tile's DMA spread among the MFMAs (1) or one burst (0); -1: the pick (1)
@@ -244,9 +244,8 @@ struct GemmArgs {
   float ln_eps = 0.f;
   // the 256x320 bf16 filter sweep's 16x16x32 MFMA form (gemm_lp_kernel MF16 = 2)
   int mf16_sweep = 0;
+  // the bf16 / fp8 tiles' IL instances (gemm_lp.hip: sweep_il)
   int issue_spread = 0;
-  int halo_mf = -1;
-  int halo_2d = -1;
 };
 
 // 64-lane sum, returned wave-uniform: DPP row_shr 1/2/4/8 sums each 16-lane
@@ -290,25 +289,16 @@ int launch_gemm_lp(rr_handle_s* h, int emode, const GemmArgs& g, hipStream_t s, 
 // B = fp16 planes [2][N][ldb] + col_scale from launch_split2h, A scaled by
 // its a_amax
 int launch_gemm_s3(rr_handle_s* h, int amode, const GemmArgs& g, hipStream_t s, int timer_cls);
-// The split core's kernel files, as h2_dispatch.hip calls them (arguments
-// checked there; n_cu: the device's CUs, st: the round stagger):
-//  h2_tile.hip: tile config cfg (4, 7, 9-12, any other value 3) on A mode
-//   amode; the implicit-GEMM stem + max-pool (h2_stem.hip's fallback)
-hipError_t launch_h2_tile(int cfg, int amode, const GemmArgs& g, hipStream_t s, int n_cu, int st);
+// The split core's kernel files: each launches the instance of its family
+// that the route names (h2_route.hpp; hipErrorInvalidValue for a tuple it has
+// none for; n_cu: the device's CUs, st: the round stagger)
+struct H2Route;
+hipError_t launch_h2_tile(const H2Route& r, int amode, const GemmArgs& g, hipStream_t s, int n_cu, int st);
+hipError_t launch_s3p(const GemmArgs& g, hipStream_t s, int n_cu, int st);  // config 8's one instance
+hipError_t launch_s3q(const H2Route& r, const GemmArgs& g, hipStream_t s, int n_cu, int st);
+hipError_t launch_h2_halo(const H2Route& r, const GemmArgs& g, hipStream_t s, int n_cu);
+// the implicit-GEMM stem + max-pool (h2_tile.hip; h2_stem.hip's fallback)
 hipError_t launch_h2_tile_stem_pool(const GemmArgs& q, hipStream_t s, int n_cu);
-//  h2_stream.hip: config 8 (dense A, N % 256 == 0)
-hipError_t launch_s3p(const GemmArgs& g, hipStream_t s, int n_cu, int st);
-//  h2_stream256.hip: config 15 (dense A) where s3q_shape and s3q_fits hold
-bool s3q_shape(const GemmArgs& g);
-bool s3q_fits(const GemmArgs& g);
-hipError_t launch_s3q(const GemmArgs& g, hipStream_t s, int n_cu, int st);
-//  h2_halo.hip: the raster halo tile (hr = h2_halo_rows(g) != 0; mf: the
-//   halo_mf form, pers: the N = 64 persistent stream) and the 2-D block tiles
-//   (where h2_halo_2d_ok)
-int h2_halo_rows(const GemmArgs& g);
-hipError_t launch_h2_halo(const GemmArgs& g, hipStream_t s, int hr, int mf, bool pers, int n_cu);
-bool h2_halo_2d_ok(const GemmArgs& g);
-hipError_t launch_h2_halo_2d(const GemmArgs& g, hipStream_t s);
 // f16x2 two-segment GEMM (GemmArgs A2 / K1): the persistent tile, N % 256 == 0
 int launch_gemm_h2_seg2(rr_handle_s* h, const GemmArgs& g, hipStream_t s, int timer_cls);
 // f16x2 NHWC4 stem conv + ReLU + 3x3/2 pad-1 max-pool (GemmArgs pool_*), N == 64

@@ -4,6 +4,7 @@ PyTorch is used only for device memory and the current HIP stream; every op
 below runs a hand-written gfx950 kernel from librr.so.  Inputs must be
 contiguous fp32 (uint8 for images) tensors on a ROCm device.
 """
+import collections
 import ctypes
 
 import torch
@@ -182,6 +183,30 @@ def conv2d_h2(x, x_amax, wc, bias, stride=1, pad=0, residual=None, relu=False, y
                                        _ptr(bias), wc.cout, wc.kh, wc.kw, stride, pad, _ptr(residual), int(relu),
                                        _ptr(y), _ptr(y_amax), _stream(dev)), hd, "rr_conv2d_h2")
     return y
+
+
+H2_ROUTE_FAMILIES = ("tile", "stream", "stream256", "halo", "halo_2d")
+_H2_ROUTE_INTS = ("family", "cfg", "wm", "wn", "fm", "fn", "bk", "hr", "tpk", "mf16", "nstg", "acc", "il", "pers", "t2")
+H2Route = collections.namedtuple("H2Route", _H2_ROUTE_INTS + ("chunk_rows",))
+
+
+class _H2RouteT(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in _H2_ROUTE_INTS] + [("chunk_rows", ctypes.c_longlong)]
+
+
+def h2_route(b, h, w, cin, cout, kh=1, kw=1, stride=1, pad=0, residual=False, relu=False, s3_cfg=0, s3_cfg_res=0,
+             halo_mf=-1, halo_2d=-1, conv_il=-1):
+    """The kernel instance conv2d_h2 runs for this shape under these tuning
+    values (rr_h2_route; host only, no GPU): an H2Route of the rr_h2_route_t
+    fields, family as its number (H2_ROUTE_FAMILIES names them).  ValueError
+    for a shape conv2d_h2 rejects or a tuning value set_tuning rejects."""
+    shape = (ctypes.c_int * 11)(b, h, w, cin, cout, kh, kw, stride, pad, int(bool(residual)), int(bool(relu)))
+    tune = (ctypes.c_int * 5)(s3_cfg, s3_cfg_res, halo_mf, halo_2d, conv_il)
+    out = _H2RouteT()
+    if _lib.lib().rr_h2_route(ctypes.cast(shape, ctypes.c_void_p), ctypes.cast(tune, ctypes.c_void_p),
+                              ctypes.cast(ctypes.pointer(out), ctypes.c_void_p)) != 0:
+        raise ValueError(f"h2_route: rr_conv2d_h2 rejects {tuple(shape)} or rr_set_tuning rejects {tuple(tune)}")
+    return H2Route(*(getattr(out, n) for n in H2Route._fields))
 
 
 def stem_pool_h2(x, x_amax, wc, bias, stride=2, pad=3, y_amax=None):
