@@ -80,10 +80,12 @@ typedef struct rr_handle_s* rr_handle_t;
  * RR_TUNE_TRUNK_PARTS (16); rr_timing_collect keeps its arguments and now
  * returns the UNION of the class's launch intervals (equal to the former sum
  * on one stream; see below); 8 = rr_h2_route was ADDED (which kernel
- * instance serves an rr_conv2d_h2 shape; no existing entry changed).
+ * instance serves an rr_conv2d_h2 shape; no existing entry changed); 9 =
+ * rr_gemm_route was ADDED (which kernel instance serves an fp32, bf16 or fp8
+ * GEMM; no existing entry changed).
  * Bindings compare rr_abi_version() with the RR_ABI_VERSION they were
  * written against.                                                          */
-#define RR_ABI_VERSION 8
+#define RR_ABI_VERSION 9
 int rr_abi_version(void);
 
 /* ---- handle ------------------------------------------------------------ */
@@ -131,7 +133,9 @@ int rr_get_device(rr_handle_t h, int* device);
  *                     value's meaning changed in ABI 5, see above),
  *                     4 (256x320 for bf16 filter / score sweeps, 256x256 otherwise),
  *                     5 (bf16 sweeps with K % 128 == 0, fp8 sweeps with K % 256 == 0:
- *                     256x256 8-phase pipeline; otherwise as 3)
+ *                     256x256 8-phase pipeline; otherwise as 3, and like 3 the 128x128
+ *                     tile where K is not a whole number of 128-byte k-tiles);
+ *                     rr_gemm_route reports what a value selects
  *   RR_TUNE_S3_CFG:   f16x2 split core, 1..15 (the table of csrc/h2_route.hpp; rr_h2_route
  *                     reports what a value selects; 1, 2, 5 and 6 are accepted and mean the
  *                     library's pick among the one-tile configs 3, 4 and 7; 13 = the halo-staged stride-1 3x3 tile on
@@ -433,6 +437,45 @@ typedef struct {
   long long chunk_rows;
 } rr_h2_route_t;
 int rr_h2_route(const rr_h2_shape_t* shape, const rr_h2_tune_t* tune, rr_h2_route_t* out);
+
+/* Which kernel instance serves a GEMM of the exact-fp32, bf16 and fp8 kernels
+ * (rr_conv2d, rr_linear*, rr_linear_bf16*, the rankers' seed and filter
+ * sweeps) under given tuning values (ABI 9).  Host only, no handle, no GPU:
+ * the same checks and the same route function (csrc/gemm_route.hpp) as the
+ * launch itself.  RR_EINVAL for a shape the launch rejects or a tuning value
+ * rr_set_tuning rejects (m == 0 or n == 0, which launches nothing, reports the
+ * route of its shape).
+ * shape: amode 0 dense A [m][lda], 1 implicit im2col (Cin % 32 == 0), 2 the
+ * generic gather, 3 NHWC4; emode 0 stored C, 1 transposed scores (the
+ * rankers' seed), 2 the filter sweep; dtype 0 fp32, 1 bf16, 2 fp8 (lda / ldb
+ * in elements); bias .. sym: the epilogue facts, 0 / 1 but activation (0
+ * none, 1 ReLU, 2 QuickGELU) and k_split (the k per split, 0 none); aligned16:
+ * A and B are 16-byte aligned.
+ * route: family -1 none (the launch fails), 0 the fp32 tile, 1 the bf16 / fp8
+ * one-tile kernel, 2 the persistent bf16 k-stream, 3 its three-A-stage form,
+ * 4 the 8-phase pipeline, 5 / 6 the hand-scheduled bf16 sweep on 128-B / 64-B
+ * LDS rows.  cfg: 22 / 41 / 88 (RR_TUNE_GEMM_CFG) for fp32, 1 to 5
+ * (RR_TUNE_LP_CFG) for bf16 / fp8 (the k-streams 3, the hand-scheduled sweep
+ * 4: their tiles).  wm .. epi: the kernel template's tuple, 0 where the family
+ * has no such parameter: wm x wn waves of fm x fn 32x32 MFMA tiles, fp32
+ * k-tile depth bk, blocks per CU minb, gl (1 = LDS-DMA staging), mf16 (1 / 2 =
+ * v_mfma_f32_16x16x32_bf16), il (the DMA spread among the MFMAs), epi (the
+ * epilogue flag set compiled in: 1 bias, 2 residual, 8 QuickGELU, 16 bf16
+ * output, 128 stats_out, 256 stats_in; -1 = flags read at run time).        */
+typedef struct {
+  int amode, emode, dtype, m, n, k;
+  long long lda, ldb, ldc;
+  int bias, residual, activation, out_bf16, stats_in, stats_out, row_scales, k_split, sym;
+  int aligned16;
+} rr_gemm_shape_t;
+typedef struct {
+  int gemm_cfg, gemm_bk, lp_cfg, sweep_form, sweep_mf16, sweep_il; /* as rr_set_tuning's keys */
+} rr_gemm_tune_t;
+typedef struct {
+  int family, cfg;
+  int wm, wn, fm, fn, bk, minb, gl, mf16, il, epi;
+} rr_gemm_route_t;
+int rr_gemm_route(const rr_gemm_shape_t* shape, const rr_gemm_tune_t* tune, rr_gemm_route_t* out);
 
 /* The output of a stage-entry bottleneck block on the f16x2 core, its 1x1
  * conv3 and its 1x1 strided downsample projection as ONE GEMM over

@@ -16,16 +16,17 @@ LIB_PATH = os.environ.get("RR_LIB_PATH") or os.path.join(_HERE, "librr.so")
 CSRC = os.path.join(_HERE, "csrc")
 
 RR_OK, RR_EINVAL, RR_EHIP, RR_EWORKSPACE, RR_EOVERFLOW = 0, -1, -2, -3, -4
-ABI_VERSION = 8  # RR_ABI_VERSION of include/rr.h these signatures follow
+ABI_VERSION = 9  # RR_ABI_VERSION of include/rr.h these signatures follow
 AMAX_SLOTS = 64  # RR_AMAX_SLOTS
 
 # timing classes (rr_timing_enable / rr_timing_collect)
 TIME_COSINE, TIME_GEMM, TIME_SELECT, TIME_ELEM, TIME_COSINE_SEED, TIME_ATTN = 0, 1, 2, 3, 4, 5
-# rr_set_tuning keys
-# (6, 7 and 12 -- sweep_order, sweep_pf, lp_il -- were retired in ABI 5)
-TUNE_GEMM_CFG, TUNE_GEMM_BK, TUNE_LP_CFG, TUNE_S3_CFG, TUNE_S3_STAGGER, \
-    TUNE_SWEEP_MF16, TUNE_SWEEP_IL, TUNE_CONV_IL, TUNE_HALO_MF, TUNE_S3_CFG_RES, TUNE_SWEEP_FORM, TUNE_HALO_2D, \
-    TUNE_TRUNK_PARTS = 1, 2, 3, 4, 5, 8, 9, 10, 11, 13, 14, 15, 16
+# rr_set_tuning: name -> (key, the default: the library's own pick)
+# (keys 6, 7 and 12 -- sweep_order, sweep_pf, lp_il -- were retired in ABI 5)
+TUNING = {"gemm_cfg": (1, 0), "gemm_bk": (2, 0), "lp_cfg": (3, 0), "s3_cfg": (4, 0), "s3_stagger": (5, -1),
+          "sweep_mf16": (8, -1), "sweep_il": (9, -1), "conv_il": (10, -1), "halo_mf": (11, -1), "s3_cfg_res": (13, 0),
+          "sweep_form": (14, -1), "halo_2d": (15, -1), "trunk_parts": (16, -1)}
+globals().update({"TUNE_" + _name.upper(): _key for _name, (_key, _) in TUNING.items()})  # TUNE_GEMM_CFG = 1, ...
 TRUNK_MAX_STAGES = 8  # RR_TRUNK_MAX_STAGES
 
 
@@ -109,6 +110,7 @@ SIGNATURES = {
     "rr_cls_attn_pool": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "rr_spp_regions": (_i, [_i, _i, _vp, _i]),
     "rr_h2_route": (_i, [_vp, _vp, _vp]),
+    "rr_gemm_route": (_i, [_vp, _vp, _vp]),
     "rr_spp_max": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "rr_spoc_refine": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     "rr_linear_groupmax": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),

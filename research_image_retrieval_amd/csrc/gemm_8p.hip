@@ -39,6 +39,7 @@
 // same lane -> k map, so each dot product covers every k once.  (The
 // 16x16x128 form of this tile left the compiler copying its accumulators and
 // spilling, 68-128 B per lane, which broke the counted waits.)
+#include "gemm_route.hpp"
 #include "gemm_tile.hpp"
 
 namespace rr {
@@ -320,17 +321,9 @@ __global__ __launch_bounds__(512, 1) void gemm_8p_kernel(GemmArgs g, int tiles_n
 
 }  // namespace
 
-// Host side: dense A and B, K a multiple of two k-tiles (bf16 128, fp8 256),
-// 16-B aligned rows (checked by launch_gemm), no split-K / symmetric; row
-// scales only for fp8.
-bool gemm_8p_eligible(const GemmArgs& g, int dt) {
-  const int ktp = dt == DT_FP8 ? 256 : 128;
-  return (dt == DT_BF16 || dt == DT_FP8) && (g.K % ktp) == 0 && g.k_split == 0 && !g.sym &&
-         (dt == DT_FP8 || (g.scale_a == nullptr && g.scale_b == nullptr)) &&
-         (((uintptr_t)g.A | (uintptr_t)g.B) & 15) == 0;
-}
-
-hipError_t launch_gemm_8p(const GemmArgs& g, int emode, hipStream_t s, int dt) {
+// The route's family GF_8P: one instance per (epilogue, dtype) of the sweeps
+hipError_t launch_gemm_8p(const GemmRoute& r, int emode, int dt, const GemmArgs& g, hipStream_t s) {
+  if (r.family != GF_8P) return hipErrorInvalidValue;
   const long long tiles_m = (g.M + 255) / 256, tiles_n = (g.N + 255) / 256;
   const long long nblk = tiles_m * tiles_n;
   if (nblk <= 0) return hipSuccess;
@@ -339,9 +332,9 @@ hipError_t launch_gemm_8p(const GemmArgs& g, int emode, hipStream_t s, int dt) {
     hipLaunchKernelGGL((gemm_8p_kernel<E_FILTER, DT_FP8>), dim3((unsigned)nblk), dim3(512), 0, s, g, (int)tiles_n);
   else if (emode == E_SCORES_T && dt == DT_FP8)
     hipLaunchKernelGGL((gemm_8p_kernel<E_SCORES_T, DT_FP8>), dim3((unsigned)nblk), dim3(512), 0, s, g, (int)tiles_n);
-  else if (emode == E_FILTER)
+  else if (emode == E_FILTER && dt == DT_BF16)
     hipLaunchKernelGGL((gemm_8p_kernel<E_FILTER, DT_BF16>), dim3((unsigned)nblk), dim3(512), 0, s, g, (int)tiles_n);
-  else if (emode == E_SCORES_T)
+  else if (emode == E_SCORES_T && dt == DT_BF16)
     hipLaunchKernelGGL((gemm_8p_kernel<E_SCORES_T, DT_BF16>), dim3((unsigned)nblk), dim3(512), 0, s, g, (int)tiles_n);
   else
     return hipErrorInvalidValue;  // stored C: the 256x256 tile of gemm_lp.hip (config 3)

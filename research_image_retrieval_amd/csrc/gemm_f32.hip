@@ -25,16 +25,14 @@
 // Block ids are remapped so consecutive tiles of one XCD share the A panel
 // (the streamed gallery / activation rows) in that XCD's L2.
 //
-// launch_gemm is the one entry point of the GEMM cores; bf16 / fp8 operands go
-// on to gemm_lp.hip.
-#include <algorithm>
-
+// launch_gemm is the one entry point of the GEMM cores: it launches the
+// instance gemm_route (gemm_route.hpp) names, here or in gemm_lp.hip,
+// gemm_lpp.hip, gemm_8p.hip and sweep16.hip.
+#include "gemm_route.hpp"
 #include "gemm_tile.hpp"
 
 namespace rr {
 
-// BK = 32: 64 KB LDS per 128x128 block, 2 blocks (2 waves/SIMD) per CU.
-// BK = 16: 32 KB, 3 blocks (3 waves/SIMD) per CU, twice the barriers.
 template <int WM, int WN, int FM, int FN, int AMODE, int EMODE, int BK, int MINB>
 __global__ __launch_bounds__(64 * WM * WN, MINB) void gemm_f32_kernel(GemmArgs g, int tiles_n) {
   constexpr int NT = 64 * WM * WN;
@@ -277,84 +275,47 @@ __global__ __launch_bounds__(64 * WM * WN, MINB) void gemm_f32_kernel(GemmArgs g
   if constexpr (EMODE == E_STORE) epilogue_store<WM, WN, FM, FN, 2 * BUF, false, -1>(g, Cb, acc, lds, m0, n0, 1.f, nullptr);
 }
 
-template <int WM, int WN, int FM, int FN, int AM, int EM, int BK, int MINB>
-static hipError_t launch_t(const GemmArgs& g, hipStream_t s) {
-  return launch_tiles<32 * FM * WM, 32 * FN * WN, 64 * WM * WN>(gemm_f32_kernel<WM, WN, FM, FN, AM, EM, BK, MINB>, g, s);
-}
-
-// k-tile depth.  Measured on MI355X (same device, interleaved A/B): BK = 16
-// (3 blocks per CU) is +2.5 % on the long-K, huge-grid cosine GEMM, BK = 32
-// (2 blocks per CU) is +4.8 % on the ResNet convs.
-static int pick_bk(int emode, const rr_handle_s::Tuning& t) {
-  if (t.gemm_bk == 16 || t.gemm_bk == 32) return t.gemm_bk;
-  return emode == E_STORE ? 32 : 16;
-}
-
-// Tile choice: both configs run 4 waves and 2 workgroups per CU (512 slots
-// on 256 CUs).  Estimated time ~ rounds x tile area, rounds = ceil(tiles /
-// 512): this charges both the padding of N (e.g. 320 queries on 128-wide
-// tiles) and the last partially-filled round (wave quantization).
-static int pick_cfg(const GemmArgs& g, int emode, const rr_handle_s::Tuning& tu) {
-  if (tu.gemm_cfg == 22 || tu.gemm_cfg == 41) return tu.gemm_cfg;
-  if (tu.gemm_cfg == 88) return (emode == E_STORE && pick_bk(emode, tu) == 32) ? 88 : 22;
-  const long long slots = pick_bk(emode, tu) == 16 ? 768 : 512;
-  const long long t22 = ((g.M + 127) / 128) * ((g.N + 127) / 128);
-  const long long t41 = ((g.M + 255) / 256) * ((g.N + 63) / 64);
-  const long long c22 = ((t22 + slots - 1) / slots) * 128 * 128;
-  const long long c41 = ((t41 + slots - 1) / slots) * 256 * 64;
-  // 88 (256x256, 1 block/CU) measured per R101 layer: +3-7 % on long-K GEMMs
-  // without a residual (3x3 256@14, 1024->512/2048), -5..-30 % on residual
-  // epilogues and short K, -40 % when the grid leaves CUs idle.  So: no
-  // residual, K >= 1024, N a multiple of 256, ~a full round.
-  if (emode == E_STORE && g.k_split == 0 && g.residual == nullptr && g.K >= 1024 && (g.N % 256) == 0 &&
-      pick_bk(emode, tu) == 32) {
-    const long long t88 = ((g.M + 255) / 256) * (g.N / 256);
-    const long long c88 = ((t88 + 255) / 256) * 256 * 256;  // 1 block/CU vs 2 for 22: compare per CU
-    if (t88 >= 240 && (double)c88 / 1.05 < (double)std::min(c22, c41) * 2.0) return 88;
-  }
-  return c41 < c22 ? 41 : 22;
-}
-
+// the instance of RR_GEMM_F32_INSTANCES that the route names, for one (A mode, epilogue)
 template <int AM, int EM>
-static hipError_t launch_cfg(const GemmArgs& g, hipStream_t s, const rr_handle_s::Tuning& tu) {
-  const int cfg = pick_cfg(g, EM, tu);
-  if (pick_bk(EM, tu) == 16) {
-    if (cfg == 41) return launch_t<4, 1, 2, 2, AM, EM, 16, 3>(g, s);
-    return launch_t<2, 2, 2, 2, AM, EM, 16, 3>(g, s);
+static hipError_t launch_f32(const GemmRoute& r, const GemmArgs& g, hipStream_t s) {
+#define RR_X(CFG, WM, WN, FM, FN, BK, MINB, WHEN)                                                               \
+  if constexpr (WHEN) {                                                                                         \
+    if (r.cfg == CFG && r.wm == WM && r.wn == WN && r.fm == FM && r.fn == FN && r.bk == BK && r.minb == MINB)   \
+      return launch_tiles<32 * FM * WM, 32 * FN * WN, 64 * WM * WN>(gemm_f32_kernel<WM, WN, FM, FN, AM, EM, BK, MINB>, g, s); \
   }
-  if (cfg == 41) return launch_t<4, 1, 2, 2, AM, EM, 32, 2>(g, s);
-  if constexpr (EM == E_STORE && (AM == A_DENSE || AM == A_CONV)) {
-    // 88: 256x256, 8 waves of 128x64, 1 block per CU
-    if (cfg == 88) return launch_t<2, 4, 4, 2, AM, EM, 32, 1>(g, s);
-  }
-  return launch_t<2, 2, 2, 2, AM, EM, 32, 2>(g, s);
+  RR_GEMM_F32_INSTANCES(RR_X)
+#undef RR_X
+  return hipErrorInvalidValue;
 }
 
+static hipError_t launch_gemm_f32(const GemmRoute& r, int amode, int emode, const GemmArgs& g, hipStream_t s) {
+  if (amode == A_DENSE && emode == E_STORE) return launch_f32<A_DENSE, E_STORE>(r, g, s);
+  if (amode == A_DENSE && emode == E_SCORES_T) return launch_f32<A_DENSE, E_SCORES_T>(r, g, s);
+  if (amode == A_DENSE && emode == E_FILTER) return launch_f32<A_DENSE, E_FILTER>(r, g, s);
+  if (amode == A_CONV && emode == E_STORE) return launch_f32<A_CONV, E_STORE>(r, g, s);
+  if (amode == A_CONV_GENERIC && emode == E_STORE) return launch_f32<A_CONV_GENERIC, E_STORE>(r, g, s);
+  if (amode == A_CONV_C4 && emode == E_STORE) return launch_f32<A_CONV_C4, E_STORE>(r, g, s);
+  return hipErrorInvalidValue;
+}
+
+// The one door of the GEMM cores: validate, route (gemm_route.hpp), launch what the route names.
 int launch_gemm(rr_handle_s* h, int amode, int emode, const GemmArgs& g, hipStream_t s, int timer_cls, int dt) {
-  if (g.M < 0 || g.N < 0 || g.K <= 0) return set_error(h, RR_EINVAL, "gemm: bad shape");
-  if (dt != DT_F32) {
-    if (amode != A_DENSE) return set_error(h, RR_EINVAL, "gemm: low-precision GEMM needs dense A");
-    return launch_gemm_lp(h, emode, g, s, timer_cls, dt);
-  }
-  if (amode != A_CONV_GENERIC && (g.K & 3) != 0) return set_error(h, RR_EINVAL, "gemm: K must be a multiple of 4");
-  if (amode == A_DENSE && (g.lda & 3)) return set_error(h, RR_EINVAL, "gemm: lda must be a multiple of 4");
-  if (amode != A_CONV_GENERIC && (g.ldb & 3) != 0) return set_error(h, RR_EINVAL, "gemm: ldb must be a multiple of 4");
-  if (emode == E_SCORES_T && (g.ldc & 3)) return set_error(h, RR_EINVAL, "gemm: ldc must be a multiple of 4");
-  if (amode == A_CONV && (g.Cin % 32) != 0) return set_error(h, RR_EINVAL, "gemm: A_CONV needs Cin % 32 == 0");
-  if ((g.k_split > 0 || g.sym) && (amode != A_DENSE || emode != E_STORE))
-    return set_error(h, RR_EINVAL, "gemm: split-K / symmetric mode needs dense A and a stored C");
-  if (g.k_split > 0 && (g.k_split % 32) != 0) return set_error(h, RR_EINVAL, "gemm: k_split must be a multiple of 32");
+  if (const char* err = gemm_shape_error(amode, emode, dt, g)) return set_error(h, RR_EINVAL, err);
   if (g.M == 0 || g.N == 0) return RR_OK;
-  hipError_t e = hipSuccess;
+  const GemmRoute r = gemm_route(amode, emode, dt, g, gemm_tune(h->tune));
+  hipError_t e = hipErrorInvalidValue;  // GF_NONE
   {
     TimedLaunch tl(h, timer_cls, s);
-    if (amode == A_DENSE && emode == E_STORE) e = launch_cfg<A_DENSE, E_STORE>(g, s, h->tune);
-    else if (amode == A_DENSE && emode == E_SCORES_T) e = launch_cfg<A_DENSE, E_SCORES_T>(g, s, h->tune);
-    else if (amode == A_DENSE && emode == E_FILTER) e = launch_cfg<A_DENSE, E_FILTER>(g, s, h->tune);
-    else if (amode == A_CONV && emode == E_STORE) e = launch_cfg<A_CONV, E_STORE>(g, s, h->tune);
-    else if (amode == A_CONV_GENERIC && emode == E_STORE) e = launch_cfg<A_CONV_GENERIC, E_STORE>(g, s, h->tune);
-    else if (amode == A_CONV_C4 && emode == E_STORE) e = launch_cfg<A_CONV_C4, E_STORE>(g, s, h->tune);
-    else return set_error(h, RR_EINVAL, "gemm: unsupported mode combination");
+    switch (r.family) {
+      case GF_F32: e = launch_gemm_f32(r, amode, emode, g, s); break;
+      case GF_LP: e = launch_gemm_lp(r, emode, dt, g, s); break;
+      case GF_LPP:
+      case GF_LPP3: e = launch_gemm_lpp(r, g, s, device_cu_count(h)); break;
+      case GF_8P: e = launch_gemm_8p(r, emode, dt, g, s); break;
+      case GF_SWEEP128:
+      case GF_SWEEP64: e = launch_sweep16(r, g, s); break;
+      default: break;
+    }
   }
   return check_hip(h, e, "gemm launch");
 }

@@ -4,7 +4,8 @@
 // the low-precision cosine rankers' seed (E_SCORES_T) and filter (E_FILTER)
 // sweeps, and the ViT linears' stored C (E_STORE, bf16 only) where the
 // persistent streams of gemm_lpp.hip do not apply.  launch_gemm
-// (gemm_f32.hip) hands every dt != DT_F32 call to launch_gemm_lp below.
+// (gemm_f32.hip) launches the instance gemm_route names through launch_gemm_lp
+// below.
 //
 // Tiling as the fp32 core's: a workgroup is WM x WN waves, a wave owns FM x FN
 // MFMA tiles of 32x32, each k-tile of A and B is a double-buffered LDS image
@@ -12,8 +13,7 @@
 // (gemm_tile.hpp swz), and block ids are remapped so consecutive tiles of one
 // XCD share the A panel.  The k-tile reaches LDS register-staged (GL = 0) or
 // by LDS-DMA (GL = 1, whole k-tiles only).
-#include <algorithm>
-
+#include "gemm_route.hpp"
 #include "gemm_tile.hpp"
 
 namespace rr {
@@ -609,183 +609,34 @@ static hipError_t launch_t1(const GemmArgs& g, hipStream_t s) {
                                                                  s);
 }
 
-// bf16 stored-C GEMMs (the ViT linears) with their epilogues compiled in:
-// QKV (bias -> bf16), out-proj / fc2 (bias + residual, fp32), fc1 (bias +
-// QuickGELU -> bf16); everything else reads its flags at run time.
-template <int WM, int WN, int FM, int FN, int EM, int DT, int MINB, int GL = 0, int MF16 = 0, int IL = 0>
-static hipError_t launch_t(const GemmArgs& g, hipStream_t s) {
-  if constexpr (EM == E_STORE && DT == DT_BF16) {
-    switch (ep_flags(g)) {
-      case EP_BIAS | EP_BF16: return launch_t1<WM, WN, FM, FN, EM, DT, MINB, GL, MF16, EP_BIAS | EP_BF16, IL>(g, s);
-      case EP_BIAS | EP_RES: return launch_t1<WM, WN, FM, FN, EM, DT, MINB, GL, MF16, EP_BIAS | EP_RES, IL>(g, s);
-      case EP_BIAS | EP_GELU | EP_BF16:
-        return launch_t1<WM, WN, FM, FN, EM, DT, MINB, GL, MF16, EP_BIAS | EP_GELU | EP_BF16, IL>(g, s);
-      default: break;
-    }
-    // the ViT LayerNorm fold (256-column tiles only; rr_linear_bf16_ln forces lp_cfg 3)
-    if constexpr (32 * FN * WN == 256 && MF16 == 1) {
-      switch (ep_flags(g)) {
-        case EP_BIAS | EP_RES | EP_STATS:
-          return launch_t1<WM, WN, FM, FN, EM, DT, MINB, GL, MF16, EP_BIAS | EP_RES | EP_STATS, IL>(g, s);
-        case EP_BIAS | EP_BF16 | EP_LNFOLD:
-          return launch_t1<WM, WN, FM, FN, EM, DT, MINB, GL, MF16, EP_BIAS | EP_BF16 | EP_LNFOLD, IL>(g, s);
-        case EP_BIAS | EP_GELU | EP_BF16 | EP_LNFOLD:
-          return launch_t1<WM, WN, FM, FN, EM, DT, MINB, GL, MF16, EP_BIAS | EP_GELU | EP_BF16 | EP_LNFOLD, IL>(g, s);
-        default: break;
-      }
-    }
-    if (g.stats_out != nullptr || g.stats_in != nullptr) return hipErrorInvalidValue;
-  }
-  return launch_t1<WM, WN, FM, FN, EM, DT, MINB, GL, MF16, -1, IL>(g, s);
-}
-
-// Configs (waves WMxWN, MFMA tiles per wave FMxFN, blocks per CU):
-//   1: 128x128, 4 waves of 64x64, 2/CU      2: 256x64, 4 waves of 64x64, 2/CU
-//   3: 256x256, 8 waves of 128x64, 1/CU (128 KB LDS) — the large GEMMs
-//   4: 256x320, 8 waves of 64x160, 1/CU (144 KB) — a 320-query batch in
-//      one tile column: the streamed gallery is read exactly once (filter
-//      and score sweeps only)
-//   5: 256x256 on the 8-phase LDS-DMA pipeline of gemm_8p.hip (bf16, K %
-//      128 == 0; picked for long-K filter sweeps whose query count 256-wide
-//      panels tile better than 320-wide ones)
-// picked by estimated rounds x tile area (rr_set_tuning(RR_TUNE_LP_CFG) forces).
-// Not kept: the 8-phase pipeline for the ViT linears (2-4 %
-// slower: short K) and the 256x320 tile on a 4-stage 64-B-row LDS-DMA ring
-// (7.59 vs 6.94 ms per C3 sweep).
-static int pick_lp(const GemmArgs& g, int emode, bool dt_bf16, const rr_handle_s::Tuning& tu) {
-  if (tu.lp_cfg >= 1 && tu.lp_cfg <= 3) return tu.lp_cfg;
-  if (tu.lp_cfg == 5) return emode == E_STORE ? 3 : 5;
-  if (tu.lp_cfg == 4) return emode == E_STORE ? 3 : 4;
-  // rounds x tile area / relative per-FLOP speed (measured, tools/lp_bench.py:
-  // the 8-wave tiles run ViT linears 1.2-1.3x faster than 128x128; the
-  // 320-query tile runs the bf16 d=2048 sweep 1.35x faster, but not d=512 or
-  // fp8, where 4-wave tiles win)
-  // (a round of `slots` resident blocks lasts ~ tile area x blocks per CU)
-  auto cost = [&](long long bm, long long bn, long long slots, double speed) {
-    const long long t = ((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn);
-    return (double)((t + slots - 1) / slots) * bm * bn * (slots / 256) / speed;
-  };
-  double best = cost(128, 128, 512, 1.0);
-  int cfg = 1;
-  if (cost(256, 64, 512, 1.0) < best) best = cost(256, 64, 512, 1.0), cfg = 2;
-  if (emode == E_STORE && cost(256, 256, 256, 1.25) < best) best = cost(256, 256, 256, 1.25), cfg = 3;
-  // filter sweeps other than the long-K bf16 one (which takes 4 below):
-  // the 8-wave 256x256 tile wins at >= 1024 queries (measured at 1280 queries
-  // x 1.6 M rows: bf16 d = 512 3.27 -> 2.39 ms, fp8 d = 2048 11.2 -> 8.1 ms
-  // per C5 step); at 320 queries the cost model keeps 128x128
-  if (emode == E_FILTER && (g.K < 1024 || g.scale_a != nullptr) && cost(256, 256, 256, 1.25) < best)
-    best = cost(256, 256, 256, 1.25), cfg = 3;
-  if (emode != E_STORE && g.K >= 1024 && g.scale_a == nullptr && cost(256, 320, 256, 1.35) < best)
-    best = cost(256, 320, 256, 1.35), cfg = 4;
-  // the 8-phase 256x256 pipeline (gemm_8p.hip) on the long-K bf16 sweeps:
-  // measured (tools/sweep_ab.py, random queries x 1.6 M x 2048) 1.22-1.25x the
-  // 256x320 tile at 256 / 512 / 768 queries (no padded query columns), 1.03x
-  // at 1280 and slower at 320 (256 + 64 padded); so it must win by padding
-  if (emode != E_STORE && dt_bf16 && g.K >= 1024 && (g.K % 128) == 0 && cost(256, 256, 256, 1.35 * 1.03) < best * 0.97)
-    best = cost(256, 256, 256, 1.35 * 1.03), cfg = 5;
-  return cfg;
-}
-
-// bf16 runs on four v_mfma_f32_16x16x32_bf16 per 32x32 tile (MF16; measured:
-// ViT-B/16 linears +4-7 %, 128x128 cosine sweeps +2-5 % over 32x32x16), except
-// the 256x320 sweep tile, whose 16x16 fragments spill (180 B/lane).
+// the instance of RR_GEMM_LP_INSTANCES and RR_GEMM_EPI_SETS that the route names, for one (epilogue, dtype)
 template <int EM, int DT>
-static hipError_t launch_lp_cfg(const GemmArgs& g, hipStream_t s, int cfg) {
-  constexpr int MF = DT == DT_BF16 ? 1 : 0;
-  if (cfg == 5) {
-    if constexpr (EM != E_STORE) {
-      if (gemm_8p_eligible(g, DT)) return launch_gemm_8p(g, EM, s, DT);
-    }
-    cfg = 3;
+static hipError_t launch_lp(const GemmRoute& r, const GemmArgs& g, hipStream_t s) {
+#define RR_E(FLAGS, FOLD, A3)                                                      \
+  if constexpr (EM == E_STORE && (!FOLD || (32 * FN_ * WN_ == 256 && MF16_ == 1))) \
+    if (r.epi == (FLAGS)) return launch_t1<WM_, WN_, FM_, FN_, EM, DT, MINB_, GL_, MF16_, (FLAGS), IL_>(g, s);
+#define RR_X(CFG, WM, WN, FM, FN, MINB, GL, MF16, IL, WHEN)                                                        \
+  if constexpr (WHEN) {                                                                                            \
+    if (r.cfg == CFG && r.wm == WM && r.wn == WN && r.fm == FM && r.fn == FN && r.bk == 0 && r.minb == MINB &&     \
+        r.gl == GL && r.mf16 == MF16 && r.il == IL) {                                                              \
+      constexpr int WM_ = WM, WN_ = WN, FM_ = FM, FN_ = FN, MINB_ = MINB, GL_ = GL, MF16_ = MF16, IL_ = IL;        \
+      RR_GEMM_EPI_SETS(RR_E)                                                                                       \
+      return r.epi == -1 ? launch_t1<WM, WN, FM, FN, EM, DT, MINB, GL, MF16, -1, IL>(g, s) : hipErrorInvalidValue; \
+    }                                                                                                              \
   }
-  switch (cfg) {
-    case 2: return launch_t<4, 1, 2, 2, EM, DT, 2, 0, MF>(g, s);
-    case 3:
-      // (the next k-tile's DMA spread among the MFMAs: sweep_il, the filter
-      // sweeps; on the ViT linears' stored-C tile it made the C4 embed slower,
-      // 61.3 -> 62.4 ms, profiles/r04k_e2e_c4_il.txt, and was removed)
-      if constexpr (EM == E_FILTER) {
-        if (g.issue_spread) return launch_t<2, 4, 4, 2, EM, DT, 1, 1, MF, 1>(g, s);
-      }
-      return launch_t<2, 4, 4, 2, EM, DT, 1, 1, MF>(g, s);
-    case 4:  // bf16 sweeps only (fp8: the 256x256 tile; its 256x320 form spills the dequantisation)
-      if constexpr (EM == E_FILTER && DT == DT_BF16) {
-        if (g.mf16_sweep && g.issue_spread) return launch_t1<4, 2, 2, 5, EM, DT, 1, 1, 2, -1, 1>(g, s);
-        if (g.mf16_sweep) return launch_t1<4, 2, 2, 5, EM, DT, 1, 1, 2>(g, s);
-        if (g.issue_spread) return launch_t1<4, 2, 2, 5, EM, DT, 1, 1, 0, -1, 1>(g, s);
-      }
-      if constexpr (EM != E_STORE && DT == DT_BF16) return launch_t<4, 2, 2, 5, EM, DT, 1, 1, 0>(g, s);
-      else if constexpr (EM != E_STORE) return launch_t<2, 4, 4, 2, EM, DT, 1, 1, MF>(g, s);
-      return hipErrorInvalidValue;
-    default: return launch_t<2, 2, 2, 2, EM, DT, 2, 0, MF>(g, s);
-  }
+  RR_GEMM_LP_INSTANCES(RR_X)
+#undef RR_X
+#undef RR_E
+  return hipErrorInvalidValue;
 }
 
-template <int EM, int DT>
-static hipError_t launch_lp(const GemmArgs& g, hipStream_t s, const rr_handle_s::Tuning& tu) {
-  static_assert(EM != E_STORE || DT == DT_BF16, "fp8 has no stored-C GEMM");
-  constexpr int EPR = DT == DT_BF16 ? 64 : 128;  // elements per 128-B k-tile row
-  int cfg = pick_lp(g, EM, DT == DT_BF16, tu);
-  if (g.stats_out != nullptr || g.stats_in != nullptr) cfg = 3;  // the LayerNorm fold: 256-column tiles
-  if ((cfg == 3 || cfg == 4) && (g.K % EPR) != 0) cfg = 1;  // LDS-DMA configs need whole k-tiles
-  if constexpr (EM == E_FILTER && DT == DT_BF16) {
-    // the hand-scheduled 16x16x32 sweep on 128-B LDS rows (sweep16.hip): the
-    // pick for K >= 1024 (the C3 prefilter's 1.6 M x 2048 sweep).  Measured
-    // against the 256x320 tile below (tools/prefilter_ab.py, 1280 queries,
-    // profiles/r06m_*): random queries 9.57 -> 7.26 ms, near-parallel 7.39 ->
-    // 7.04, and 6.86 -> 7.01 on identical queries (the bench's random-weight
-    // descriptors); at K = 512 (C4) 2.43 -> 2.49 ms, so short K keeps the tile
-    const int form = tu.sweep_form >= 0 ? tu.sweep_form : (g.K >= 1024 && (g.K % 64) == 0 ? 1 : 0);
-    if ((form == 1 || form == 2) && sweep16_eligible(g)) return launch_sweep16(g, s, form == 1);
-  }
-  if constexpr (EM == E_FILTER) {
-    // the 256x320 bf16 tile's default: v_mfma_f32_32x32x16_bf16 with the next
-    // k-tile's DMA spread among the MFMAs (sweep_il).  On the C3 bench's own
-    // descriptors (tools/e2e_ab.py, profiles/r04j_e2e_ab.txt): 7.15 -> 6.81
-    // ms; the 16x16x32 form is 7.71 ms there (7.08 with the spread), though
-    // it won on synthetic near-parallel queries (r04f_sweep_il_ab.txt).
-    // Bit-identical rankings in every form.
-    GemmArgs g2 = g;
-    g2.mf16_sweep = tu.sweep_mf16 > 0;
-    // (sweep_il = 1 spreads every filter sweep's DMA, the 256x256 bf16 one
-    // too; the default: the 256x320 bf16 and the fp8 sweeps -- C5's fp8
-    // sweeps 7.70 -> 7.53 ms per step on the bench, profiles/r04k_c5_*.json)
-    g2.issue_spread = tu.sweep_il > 0 || (tu.sweep_il < 0 && ((cfg == 4 && DT == DT_BF16) || DT == DT_FP8));
-    return launch_lp_cfg<EM, DT>(g2, s, cfg);
-  }
-  return launch_lp_cfg<EM, DT>(g, s, cfg);
-}
-
-int launch_gemm_lp(rr_handle_s* h, int emode, const GemmArgs& g, hipStream_t s, int timer_cls, int dt) {
-  const int vec = dt == DT_BF16 ? 8 : 16;  // elements per 16-B staging load
-  if ((g.K % vec) || (g.lda % vec) || (g.ldb % vec))
-    return set_error(h, RR_EINVAL, "gemm: low-precision K / lda / ldb must be multiples of 16 bytes");
-  if (emode == E_SCORES_T && (g.ldc & 3)) return set_error(h, RR_EINVAL, "gemm: ldc must be a multiple of 4");
-  if (dt == DT_FP8 && emode == E_STORE) return set_error(h, RR_EINVAL, "gemm: fp8 has no stored-C GEMM");
-  if (g.M == 0 || g.N == 0) return RR_OK;
-  hipError_t e = hipSuccess;
-  {
-    TimedLaunch tl(h, timer_cls, s);
-    if (dt == DT_BF16) {
-      // the ViT linears' epilogue flag sets with K <= 1024: the persistent
-      // 256x256 k-stream (gemm_lpp.hip), with three A stages where the
-      // fold's LDS is not needed (lp_cfg 3 forces the one-tile kernel; 6
-      // the three-A-stage form for the no-fold flag sets at any K).  Per
-      // block of linears 4.51 -> 4.35 ms (profiles/r05u_vitlin.txt); the C4
-      // embed 62.29 -> 61.54 ms with the first form (r05q_e2e_c4.txt)
-      if (emode == E_STORE && lpp3_eligible(g) && (h->tune.lp_cfg == 6 || (h->tune.lp_cfg == 0 && g.K <= 1024)))
-        e = launch_lpp3(g, s, device_cu_count(h));
-      else if (emode == E_STORE && (h->tune.lp_cfg == 0 || h->tune.lp_cfg == 6) && lpp_eligible(g))
-        e = launch_lpp(g, s, device_cu_count(h));
-      else if (emode == E_STORE) e = launch_lp<E_STORE, DT_BF16>(g, s, h->tune);
-      else if (emode == E_SCORES_T) e = launch_lp<E_SCORES_T, DT_BF16>(g, s, h->tune);
-      else e = launch_lp<E_FILTER, DT_BF16>(g, s, h->tune);
-    } else {
-      if (emode == E_SCORES_T) e = launch_lp<E_SCORES_T, DT_FP8>(g, s, h->tune);
-      else e = launch_lp<E_FILTER, DT_FP8>(g, s, h->tune);
-    }
-  }
-  return check_hip(h, e, "gemm launch");
+hipError_t launch_gemm_lp(const GemmRoute& r, int emode, int dt, const GemmArgs& g, hipStream_t s) {
+  if (dt == DT_BF16 && emode == E_STORE) return launch_lp<E_STORE, DT_BF16>(r, g, s);
+  if (dt == DT_BF16 && emode == E_SCORES_T) return launch_lp<E_SCORES_T, DT_BF16>(r, g, s);
+  if (dt == DT_BF16 && emode == E_FILTER) return launch_lp<E_FILTER, DT_BF16>(r, g, s);
+  if (dt == DT_FP8 && emode == E_SCORES_T) return launch_lp<E_SCORES_T, DT_FP8>(r, g, s);
+  if (dt == DT_FP8 && emode == E_FILTER) return launch_lp<E_FILTER, DT_FP8>(r, g, s);
+  return hipErrorInvalidValue;  // fp8 has no stored-C GEMM
 }
 
 }  // namespace rr

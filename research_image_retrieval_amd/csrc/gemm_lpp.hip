@@ -26,10 +26,9 @@
 // (c_fc 1.744, c_proj 1.498 ms, r05p_vitlin.txt): twice the barriers.
 //
 // Operands: A [M][K] bf16 (lda), B [N][K] bf16 (ldb), K % 64 == 0, K <= 1024,
-// N % 256 == 0 (lpp_eligible).  Rows past M read row M - 1 (never stored).
+// N % 256 == 0 (gemm_route.hpp lpp_eligible).  Rows past M read row M - 1 (never stored).
 
-#include <algorithm>
-
+#include "gemm_route.hpp"
 #include "gemm_tile.hpp"
 
 namespace rr {
@@ -500,19 +499,8 @@ __global__ __launch_bounds__(512, 1) void gemm_lpp3_kernel(GemmArgs g, int tiles
   }
 }
 
-template <int EPI>
-static hipError_t launch_lpp3_t(GemmArgs g, hipStream_t s, int n_cu) {
-  const long long tiles_m = (g.M + 255) / 256, tiles_n = g.N / 256;
-  const long long ntiles = tiles_m * tiles_n;
-  if (ntiles <= 0) return hipSuccess;
-  if (ntiles * (g.K / 64) > 0x7fffffffLL) return hipErrorInvalidValue;
-  const int slots = std::max(8, n_cu & ~7);
-  const int grid = ntiles <= slots ? (int)ntiles : slots;
-  hipLaunchKernelGGL((gemm_lpp3_kernel<EPI>), dim3((unsigned)grid), dim3(512), 0, s, g, (int)tiles_n, (int)ntiles);
-  return hipGetLastError();
-}
-
-template <int EPI>
+// FAMILY: GF_LPP the k-stream, GF_LPP3 its three-A-stage form
+template <int EPI, int FAMILY>
 static hipError_t launch_lpp_t(GemmArgs g, hipStream_t s, int n_cu) {
   const long long tiles_m = (g.M + 255) / 256, tiles_n = g.N / 256;
   const long long ntiles = tiles_m * tiles_n;
@@ -521,58 +509,24 @@ static hipError_t launch_lpp_t(GemmArgs g, hipStream_t s, int n_cu) {
   // one block per CU; a block that owns several tiles stays on its XCD (grid a multiple of 8)
   const int slots = std::max(8, n_cu & ~7);
   const int grid = ntiles <= slots ? (int)ntiles : slots;
-  hipLaunchKernelGGL((gemm_lpp_kernel<EPI>), dim3((unsigned)grid), dim3(512), 0, s, g, (int)tiles_n, (int)ntiles);
+  if constexpr (FAMILY == GF_LPP3)
+    hipLaunchKernelGGL((gemm_lpp3_kernel<EPI>), dim3((unsigned)grid), dim3(512), 0, s, g, (int)tiles_n, (int)ntiles);
+  else
+    hipLaunchKernelGGL((gemm_lpp_kernel<EPI>), dim3((unsigned)grid), dim3(512), 0, s, g, (int)tiles_n, (int)ntiles);
   return hipGetLastError();
 }
 
 }  // namespace
 
-// The ViT linears' epilogue flag sets (as gemm_lp.hip launch_t); other flag
-// sets return hipErrorNotSupported (the caller runs the one-tile kernel).
-bool lpp_eligible(const GemmArgs& g) {
-  // (K <= 1024: c_proj, K = 3072, ran 11 % slower than the one-tile kernel)
-  if (g.M <= 0 || (g.N % 256) != 0 || (g.K % 64) != 0 || g.K > 1024 || g.k_split > 0 || g.sym) return false;
-  switch (ep_flags(g)) {
-    case EP_BIAS | EP_BF16:
-    case EP_BIAS | EP_RES:
-    case EP_BIAS | EP_GELU | EP_BF16:
-    case EP_BIAS | EP_RES | EP_STATS:
-    case EP_BIAS | EP_BF16 | EP_LNFOLD:
-    case EP_BIAS | EP_GELU | EP_BF16 | EP_LNFOLD: return true;
-    default: return false;
-  }
-}
-
-// The three-A-stage form: the pick for the no-fold flag sets with K <= 1024
-// (out-proj 0.579 -> 0.546 ms against the two-stage form, r05u_vitlin.txt);
-// at K = 3072 (c_proj) it ran 1.313 ms against the one-tile kernel's 1.257,
-// so lp_cfg 6 (tests) is the only way there.
-bool lpp3_eligible(const GemmArgs& g) {
-  if (g.M <= 0 || (g.N % 256) != 0 || (g.K % 64) != 0 || g.k_split > 0 || g.sym) return false;
-  const int f = ep_flags(g);
-  return f == (EP_BIAS | EP_BF16) || f == (EP_BIAS | EP_RES) || f == (EP_BIAS | EP_GELU | EP_BF16) ||
-         f == (EP_BIAS | EP_RES | EP_STATS);
-}
-hipError_t launch_lpp3(const GemmArgs& g, hipStream_t s, int n_cu) {
-  switch (ep_flags(g)) {
-    case EP_BIAS | EP_BF16: return launch_lpp3_t<EP_BIAS | EP_BF16>(g, s, n_cu);
-    case EP_BIAS | EP_RES: return launch_lpp3_t<EP_BIAS | EP_RES>(g, s, n_cu);
-    case EP_BIAS | EP_GELU | EP_BF16: return launch_lpp3_t<EP_BIAS | EP_GELU | EP_BF16>(g, s, n_cu);
-    case EP_BIAS | EP_RES | EP_STATS: return launch_lpp3_t<EP_BIAS | EP_RES | EP_STATS>(g, s, n_cu);
-    default: return hipErrorNotSupported;
-  }
-}
-
-hipError_t launch_lpp(const GemmArgs& g, hipStream_t s, int n_cu) {
-  switch (ep_flags(g)) {
-    case EP_BIAS | EP_BF16: return launch_lpp_t<EP_BIAS | EP_BF16>(g, s, n_cu);
-    case EP_BIAS | EP_RES: return launch_lpp_t<EP_BIAS | EP_RES>(g, s, n_cu);
-    case EP_BIAS | EP_GELU | EP_BF16: return launch_lpp_t<EP_BIAS | EP_GELU | EP_BF16>(g, s, n_cu);
-    case EP_BIAS | EP_RES | EP_STATS: return launch_lpp_t<EP_BIAS | EP_RES | EP_STATS>(g, s, n_cu);
-    case EP_BIAS | EP_BF16 | EP_LNFOLD: return launch_lpp_t<EP_BIAS | EP_BF16 | EP_LNFOLD>(g, s, n_cu);
-    case EP_BIAS | EP_GELU | EP_BF16 | EP_LNFOLD: return launch_lpp_t<EP_BIAS | EP_GELU | EP_BF16 | EP_LNFOLD>(g, s, n_cu);
-    default: return hipErrorNotSupported;
-  }
+// The k-stream (GF_LPP) or its three-A-stage form (GF_LPP3) with the route's
+// compiled-in epilogue flag set (RR_GEMM_EPI_SETS; A3: the sets the latter has)
+hipError_t launch_gemm_lpp(const GemmRoute& r, const GemmArgs& g, hipStream_t s, int n_cu) {
+#define RR_X(FLAGS, FOLD, A3)                                                                    \
+  if (r.epi == (FLAGS) && r.family == GF_LPP) return launch_lpp_t<(FLAGS), GF_LPP>(g, s, n_cu); \
+  if (r.epi == (FLAGS) && r.family == GF_LPP3 && A3) return launch_lpp_t<(FLAGS), A3 ? GF_LPP3 : GF_LPP>(g, s, n_cu);
+  RR_GEMM_EPI_SETS(RR_X)
+#undef RR_X
+  return hipErrorInvalidValue;
 }
 
 }  // namespace rr

@@ -1,9 +1,9 @@
 // rr_api.hip — C-ABI entry points of librr (see include/rr.h).
 #include <algorithm>
 #include <cstring>
-#include <initializer_list>
 
 #include "gemm_epilogue.hpp"
+#include "gemm_route.hpp"
 #include "h2_route.hpp"
 #include "rr_internal.hpp"
 
@@ -72,6 +72,42 @@ static TopkWs topk_layout(int nq, long long n, int k, long long cap = -1) {
   return w;
 }
 
+// rr_set_tuning's keys: the Tuning member each sets and the values it takes
+// (lo .. hi, or the n values of set).  rr_h2_route and rr_gemm_route check
+// their tuning values against the same rows.
+struct TuneRow {
+  int key;
+  int rr_handle_s::Tuning::*field;
+  int lo, hi, n, set[4];
+};
+using Tuning = rr_handle_s::Tuning;
+static const TuneRow kTuneRows[] = {
+    {RR_TUNE_GEMM_CFG, &Tuning::gemm_cfg, 0, 0, 4, {0, 22, 41, 88}},
+    {RR_TUNE_GEMM_BK, &Tuning::gemm_bk, 0, 0, 3, {0, 16, 32}},
+    {RR_TUNE_LP_CFG, &Tuning::lp_cfg, 0, 6},
+    {RR_TUNE_S3_CFG, &Tuning::s3_cfg, 0, 15},
+    {RR_TUNE_S3_STAGGER, &Tuning::s3_stagger, -1, 200},
+    {RR_TUNE_SWEEP_MF16, &Tuning::sweep_mf16, -1, 1},
+    {RR_TUNE_SWEEP_IL, &Tuning::sweep_il, -1, 1},
+    {RR_TUNE_CONV_IL, &Tuning::conv_il, -1, 1},
+    {RR_TUNE_HALO_MF, &Tuning::halo_mf, -1, 4},
+    {RR_TUNE_S3_CFG_RES, &Tuning::s3_cfg_res, 0, 15},
+    {RR_TUNE_SWEEP_FORM, &Tuning::sweep_form, -1, 2},
+    {RR_TUNE_HALO_2D, &Tuning::halo_2d, -1, 1},
+    {RR_TUNE_TRUNK_PARTS, &Tuning::trunk_parts, 0, 0, 3, {-1, 1, 2}},
+};
+static const TuneRow* tune_row(int key) {
+  for (const TuneRow& r : kTuneRows)
+    if (r.key == key) return &r;
+  return nullptr;
+}
+static bool tuning_value_ok(int key, int value) {
+  const TuneRow* r = tune_row(key);
+  if (!r) return false;
+  if (r->n == 0) return value >= r->lo && value <= r->hi;
+  return std::find(r->set, r->set + r->n, value) != r->set + r->n;
+}
+
 }  // namespace rr
 
 using namespace rr;
@@ -124,68 +160,11 @@ int rr_get_device(rr_handle_t h, int* device) {
 
 int rr_set_tuning(rr_handle_t h, int key, int value) {
   if (!h) return RR_EINVAL;
-  auto in = [&](std::initializer_list<int> ok) {
-    for (int v : ok)
-      if (v == value) return true;
-    return false;
-  };
-  switch (key) {
-    case RR_TUNE_GEMM_CFG:
-      if (!in({0, 22, 41, 88})) break;
-      h->tune.gemm_cfg = value;
-      return RR_OK;
-    case RR_TUNE_GEMM_BK:
-      if (!in({0, 16, 32})) break;
-      h->tune.gemm_bk = value;
-      return RR_OK;
-    case RR_TUNE_LP_CFG:
-      if (value < 0 || value > 6) break;
-      h->tune.lp_cfg = value;
-      return RR_OK;
-    case RR_TUNE_S3_CFG:
-      if (value < 0 || value > 15) break;
-      h->tune.s3_cfg = value;
-      return RR_OK;
-    case RR_TUNE_S3_STAGGER:
-      if (value < -1 || value > 200) break;
-      h->tune.s3_stagger = value;
-      return RR_OK;
-    case RR_TUNE_SWEEP_MF16:
-      if (!in({-1, 0, 1})) break;
-      h->tune.sweep_mf16 = value;
-      return RR_OK;
-    case RR_TUNE_SWEEP_IL:
-      if (!in({-1, 0, 1})) break;
-      h->tune.sweep_il = value;
-      return RR_OK;
-    case RR_TUNE_CONV_IL:
-      if (!in({-1, 0, 1})) break;
-      h->tune.conv_il = value;
-      return RR_OK;
-    case RR_TUNE_HALO_MF:
-      if (!in({-1, 0, 1, 2, 3, 4})) break;
-      h->tune.halo_mf = value;
-      return RR_OK;
-    case RR_TUNE_S3_CFG_RES:
-      if (value < 0 || value > 15) break;
-      h->tune.s3_cfg_res = value;
-      return RR_OK;
-    case RR_TUNE_SWEEP_FORM:
-      if (!in({-1, 0, 1, 2})) break;
-      h->tune.sweep_form = value;
-      return RR_OK;
-    case RR_TUNE_HALO_2D:
-      if (!in({-1, 0, 1})) break;
-      h->tune.halo_2d = value;
-      return RR_OK;
-    case RR_TUNE_TRUNK_PARTS:
-      if (!in({-1, 1, 2})) break;
-      h->tune.trunk_parts = value;
-      return RR_OK;
-    default:
-      return set_error(h, RR_EINVAL, "rr_set_tuning: unknown key");
-  }
-  return set_error(h, RR_EINVAL, "rr_set_tuning: value out of range for this key");
+  const TuneRow* row = tune_row(key);
+  if (!row) return set_error(h, RR_EINVAL, "rr_set_tuning: unknown key");
+  if (!tuning_value_ok(key, value)) return set_error(h, RR_EINVAL, "rr_set_tuning: value out of range for this key");
+  h->tune.*(row->field) = value;
+  return RR_OK;
 }
 
 // The class's launch intervals on one time axis (offsets from its first start
@@ -583,8 +562,9 @@ int rr_conv2d_h2(rr_handle_t h, const float* x, const unsigned* x_amax, int b, i
 
 int rr_h2_route(const rr_h2_shape_t* sh, const rr_h2_tune_t* tu, rr_h2_route_t* out) {
   if (!sh || !tu || !out || (sh->residual & ~1)) return RR_EINVAL;
-  if (tu->s3_cfg < 0 || tu->s3_cfg > 15 || tu->s3_cfg_res < 0 || tu->s3_cfg_res > 15 || tu->halo_mf < -1 ||
-      tu->halo_mf > 4 || tu->halo_2d < -1 || tu->halo_2d > 1 || tu->conv_il < -1 || tu->conv_il > 1)
+  if (!tuning_value_ok(RR_TUNE_S3_CFG, tu->s3_cfg) || !tuning_value_ok(RR_TUNE_S3_CFG_RES, tu->s3_cfg_res) ||
+      !tuning_value_ok(RR_TUNE_HALO_MF, tu->halo_mf) || !tuning_value_ok(RR_TUNE_HALO_2D, tu->halo_2d) ||
+      !tuning_value_ok(RR_TUNE_CONV_IL, tu->conv_il))
     return RR_EINVAL;
   GemmArgs g;
   int amode;
@@ -601,6 +581,42 @@ int rr_h2_route(const rr_h2_shape_t* sh, const rr_h2_tune_t* tu, rr_h2_route_t* 
   t.conv_il = tu->conv_il;
   const H2Route r = h2_route(amode, g, h2_tune(t, sh->residual != 0));
   *out = {r.family, r.cfg, r.wm, r.wn, r.fm, r.fn, r.bk, r.hr, r.tpk, r.mf16, r.nstg, r.acc, r.il, r.pers, r.t2, r.chunk_rows};
+  return RR_OK;
+}
+
+int rr_gemm_route(const rr_gemm_shape_t* sh, const rr_gemm_tune_t* tu, rr_gemm_route_t* out) {
+  if (!sh || !tu || !out) return RR_EINVAL;
+  if (!tuning_value_ok(RR_TUNE_GEMM_CFG, tu->gemm_cfg) || !tuning_value_ok(RR_TUNE_GEMM_BK, tu->gemm_bk) ||
+      !tuning_value_ok(RR_TUNE_LP_CFG, tu->lp_cfg) || !tuning_value_ok(RR_TUNE_SWEEP_FORM, tu->sweep_form) ||
+      !tuning_value_ok(RR_TUNE_SWEEP_MF16, tu->sweep_mf16) || !tuning_value_ok(RR_TUNE_SWEEP_IL, tu->sweep_il))
+    return RR_EINVAL;
+  if (sh->amode < A_DENSE || sh->amode > A_CONV_C4 || sh->emode < E_STORE || sh->emode > E_FILTER || sh->dtype < DT_F32 ||
+      sh->dtype > DT_FP8 || sh->activation < 0 || sh->activation > 2)
+    return RR_EINVAL;
+  // (the route asks of a pointer only whether there is one, and of A and B their low four bits)
+  const float* const some = reinterpret_cast<const float*>((uintptr_t)16);
+  GemmArgs g;
+  g.A = g.B = reinterpret_cast<const float*>((uintptr_t)(sh->aligned16 ? 16 : 4));
+  g.M = sh->m;
+  g.N = sh->n;
+  g.K = sh->k;
+  g.lda = sh->lda;
+  g.ldb = sh->ldb;
+  g.ldc = sh->ldc;
+  if (sh->amode != A_DENSE) g.Cin = 32;  // (a conv's geometry does not steer the route; A_CONV needs Cin % 32 == 0)
+  if (sh->bias) g.bias = some;
+  if (sh->residual) g.residual = some;
+  g.relu = sh->activation;
+  g.out_bf16 = sh->out_bf16 != 0;
+  if (sh->stats_in) g.stats_in = some;
+  if (sh->stats_out) g.stats_out = const_cast<float*>(some);
+  if (sh->row_scales) g.scale_a = g.scale_b = some;
+  g.k_split = sh->k_split;
+  g.sym = sh->sym != 0;
+  if (gemm_shape_error(sh->amode, sh->emode, sh->dtype, g)) return RR_EINVAL;
+  const GemmRoute r = gemm_route(sh->amode, sh->emode, sh->dtype, g, {tu->gemm_cfg, tu->gemm_bk, tu->lp_cfg, tu->sweep_form,
+                                                                     tu->sweep_mf16, tu->sweep_il});
+  *out = {r.family, r.cfg, r.wm, r.wn, r.fm, r.fn, r.bk, r.minb, r.gl, r.mf16, r.il, r.epi};
   return RR_OK;
 }
 

@@ -242,10 +242,6 @@ struct GemmArgs {
   const float* colsum = nullptr;
   int stats_k = 0;
   float ln_eps = 0.f;
-  // the 256x320 bf16 filter sweep's 16x16x32 MFMA form (gemm_lp_kernel MF16 = 2)
-  int mf16_sweep = 0;
-  // the bf16 / fp8 tiles' IL instances (gemm_lp.hip: sweep_il)
-  int issue_spread = 0;
 };
 
 // 64-lane sum, returned wave-uniform: DPP row_shr 1/2/4/8 sums each 16-lane
@@ -278,11 +274,22 @@ __device__ __forceinline__ void tile_coords(int bid, int nwg, int tiles_n, int& 
   tm = wgid / tiles_n;
 }
 
+// The one door of the fp32, bf16 and fp8 GEMM kernels (gemm_f32.hip): it
+// launches the instance gemm_route names (gemm_route.hpp)
 int launch_gemm(rr_handle_s* h, int amode, int emode, const GemmArgs& a, hipStream_t s, int timer_cls,
                 int dt = DT_F32);
-// the bf16 / fp8 half of launch_gemm (gemm_lp.hip; dense A): its checks and
-// the choice among the one-tile kernels, gemm_lpp.hip, gemm_8p.hip and sweep16.hip
-int launch_gemm_lp(rr_handle_s* h, int emode, const GemmArgs& g, hipStream_t s, int timer_cls, int dt);
+// The low-precision kernel files: each launches the instance of its family
+// that the route names (hipErrorInvalidValue for a tuple it has none for;
+// n_cu: the device's CUs).  gemm_lp.hip: one tile per block; gemm_lpp.hip: the
+// bf16 stored-C GEMM as a persistent 256x256 k-stream; gemm_8p.hip: the 256x256
+// 8-phase pipeline (16x16x128 block-scaled MFMA for fp8); sweep16.hip: the
+// bf16 filter sweep on 16x16x32 MFMA with a hand-placed k-loop (256 gallery
+// rows x 320 queries per block, 8 waves)
+struct GemmRoute;
+hipError_t launch_gemm_lp(const GemmRoute& r, int emode, int dt, const GemmArgs& g, hipStream_t s);
+hipError_t launch_gemm_lpp(const GemmRoute& r, const GemmArgs& g, hipStream_t s, int n_cu);
+hipError_t launch_gemm_8p(const GemmRoute& r, int emode, int dt, const GemmArgs& g, hipStream_t s);
+hipError_t launch_sweep16(const GemmRoute& r, const GemmArgs& g, hipStream_t s);
 
 // fp32-accurate GEMM on the 16-bit matrix cores (the f16x2 split core,
 // h2_dispatch.hip): A fp32 (A_DENSE, A_CONV or A_CONV_C4), E_STORE epilogue;
@@ -310,11 +317,6 @@ int launch_split2h(rr_handle_s* h, const float* w, int rows, int k, int kpad, ui
 // max |x| over x[n] into the RR_AMAX_SLOTS words at slots (atomic max)
 int launch_amax(rr_handle_s* h, const float* x, long long n, uint32_t* slots, hipStream_t s);
 
-// 256x256 8-phase pipeline (gemm_8p.hip), bf16 or fp8 (16x16x128 block-scaled
-// MFMA): dense A/B, K a multiple of two k-tiles
-bool gemm_8p_eligible(const GemmArgs& g, int dt);
-hipError_t launch_gemm_8p(const GemmArgs& g, int emode, hipStream_t s, int dt);
-
 // ---- top-k kernels (topk.hip) -------------------------------------------
 // Dense scores, query-major [nq][ld] (first `rows` valid) -> per query the
 // top-min(k,rows) keys written to cand[q][0..), cnt[q], tau[q].
@@ -331,17 +333,5 @@ int launch_prefilter_rescore(rr_handle_s* h, unsigned long long* cand, long long
                              const float* eps2, float* t2, const float* q, const float* g, int d, hipStream_t s);
 int launch_merge(rr_handle_s* h, const float* ps, const long long* pi, int nparts, int nq, int kin,
                  int kout, float* os, long long* oi, hipStream_t s);
-
-// sweep16.hip: the bf16 filter sweep on 16x16x32 MFMA with a hand-placed
-// k-loop (256 gallery rows x 320 queries per block, 8 waves); rows128: LDS
-// rows of 128 B (K % 64 == 0; else 64-B rows)
-bool sweep16_eligible(const GemmArgs& g);
-hipError_t launch_sweep16(const GemmArgs& g, hipStream_t s, int rows128);
-
-// gemm_lpp.hip: the bf16 stored-C GEMM as a persistent 256x256 k-stream
-bool lpp_eligible(const GemmArgs& g);
-hipError_t launch_lpp(const GemmArgs& g, hipStream_t s, int n_cu);
-bool lpp3_eligible(const GemmArgs& g);
-hipError_t launch_lpp3(const GemmArgs& g, hipStream_t s, int n_cu);
 
 }  // namespace rr

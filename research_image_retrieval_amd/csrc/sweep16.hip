@@ -31,7 +31,7 @@
 // The bf16 products are exact in fp32 and the accumulation order is covered
 // by the prefilter's bound (prefilter.hip), so the exact ranker's output does
 // not depend on which sweep ran (tests/test_gpu_rank.py).
-#include "rr_internal.hpp"
+#include "gemm_route.hpp"
 
 namespace rr {
 namespace {
@@ -39,7 +39,7 @@ namespace {
 typedef float sw_f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 sw_bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int SW_BM = 256, SW_BN = 320, SW_ROWS = SW_BM + SW_BN;
+constexpr int SW_ROWS = SW_BM + SW_BN;  // (gemm_route.hpp: SW_BM = 256 gallery rows, SW_BN = 320 queries)
 constexpr int SW_STAGE = SW_ROWS * 64;  // bytes per stage: 576 rows x 32 bf16
 constexpr int SW_NST = 4;
 constexpr int SW_NCH = SW_ROWS / 16;  // LDS-DMA instructions per stage (16 rows x 64 B each)
@@ -761,23 +761,19 @@ __global__ __launch_bounds__(512, 1) void sweep128_kernel(GemmArgs g, int tiles_
 
 }  // namespace
 
-bool sweep16_eligible(const GemmArgs& g) {
-  return g.K > 0 && (g.K % 32) == 0 && (g.lda % 8) == 0 && (g.ldb % 8) == 0 && g.scale_a == nullptr &&
-         g.scale_b == nullptr && ((uintptr_t)g.A & 15) == 0 && ((uintptr_t)g.B & 15) == 0 &&
-         (long long)SW_BM * g.lda * 2 < (1LL << 31) && (long long)SW_BN * g.ldb * 2 < (1LL << 31);
-}
-
-// rows128: the 128-B-row kernel (K % 64 == 0), else the 64-B-row one
-hipError_t launch_sweep16(const GemmArgs& g, hipStream_t s, int rows128) {
+// The route's family: GF_SWEEP128 the 128-B-row kernel (K % 64 == 0), GF_SWEEP64 the 64-B-row one
+hipError_t launch_sweep16(const GemmRoute& r, const GemmArgs& g, hipStream_t s) {
   const long long tiles_m = (g.M + SW_BM - 1) / SW_BM;
   const long long tiles_n = (g.N + SW_BN - 1) / SW_BN;
   const long long nblk = tiles_m * tiles_n;
   if (nblk <= 0) return hipSuccess;
   if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
-  if (rows128 && (g.K % 64) == 0)
+  if (r.family == GF_SWEEP128 && (g.K % 64) == 0)
     hipLaunchKernelGGL(sweep128_kernel<0>, dim3((unsigned)nblk), dim3(512), 0, s, g, (int)tiles_n, (int)nblk);
-  else
+  else if (r.family == GF_SWEEP64)
     hipLaunchKernelGGL(sweep16_kernel<8>, dim3((unsigned)nblk), dim3(512), 0, s, g, (int)tiles_n);
+  else
+    return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

@@ -209,6 +209,45 @@ def h2_route(b, h, w, cin, cout, kh=1, kw=1, stride=1, pad=0, residual=False, re
     return H2Route(*(getattr(out, n) for n in H2Route._fields))
 
 
+GEMM_ROUTE_FAMILIES = ("f32", "lp", "lpp", "lpp3", "8p", "sweep128", "sweep64")  # family -1: no instance
+GEMM_AMODES = {"dense": 0, "conv": 1, "conv_generic": 2, "conv_c4": 3}
+GEMM_EMODES = {"store": 0, "scores_t": 1, "filter": 2}
+GEMM_DTYPES = {"f32": 0, "bf16": 1, "fp8": 2}
+EP_BIAS, EP_RES, EP_GELU, EP_BF16, EP_STATS, EP_LNFOLD = 1, 2, 8, 16, 128, 256  # GemmRoute.epi's flags
+GemmRoute = collections.namedtuple("GemmRoute", ("family", "cfg", "wm", "wn", "fm", "fn", "bk", "minb", "gl", "mf16", "il",
+                                                 "epi"))
+
+
+class _GemmShapeT(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_int) for n in ("amode", "emode", "dtype", "m", "n", "k")] +
+                [(n, ctypes.c_longlong) for n in ("lda", "ldb", "ldc")] +
+                [(n, ctypes.c_int) for n in ("bias", "residual", "activation", "out_bf16", "stats_in", "stats_out",
+                                             "row_scales", "k_split", "sym", "aligned16")])
+
+
+def gemm_route(m, n, k, dtype="f32", emode="store", amode="dense", lda=None, ldb=None, ldc=None, bias=False,
+               residual=False, activation=0, out_bf16=False, stats_in=False, stats_out=False, row_scales=False, k_split=0,
+               sym=False, aligned16=True, gemm_cfg=0, gemm_bk=0, lp_cfg=0, sweep_form=-1, sweep_mf16=-1, sweep_il=-1):
+    """The kernel instance that serves the GEMM C[m, n] = A[m, k] . B[n, k]^T
+    of the fp32, bf16 and fp8 kernels under these tuning values (rr_gemm_route;
+    host only, no GPU): a GemmRoute of the rr_gemm_route_t fields, family as
+    its number (GEMM_ROUTE_FAMILIES names them).  lda / ldb default to k, ldc
+    to n (scores_t: m rounded up to 4).  ValueError for a shape the launch
+    rejects or a tuning value set_tuning rejects."""
+    em = GEMM_EMODES[emode]
+    shape = _GemmShapeT(GEMM_AMODES[amode], em, GEMM_DTYPES[dtype], m, n, k, k if lda is None else lda,
+                        k if ldb is None else ldb, ((m + 3) // 4 * 4 if em == 1 else n) if ldc is None else ldc, int(bool(bias)),
+                        int(bool(residual)), int(activation), int(bool(out_bf16)), int(bool(stats_in)), int(bool(stats_out)),
+                        int(bool(row_scales)), k_split, int(bool(sym)), int(bool(aligned16)))
+    tune = (ctypes.c_int * 6)(gemm_cfg, gemm_bk, lp_cfg, sweep_form, sweep_mf16, sweep_il)
+    out = (ctypes.c_int * len(GemmRoute._fields))()
+    if _lib.lib().rr_gemm_route(ctypes.cast(ctypes.pointer(shape), ctypes.c_void_p), ctypes.cast(tune, ctypes.c_void_p),
+                                ctypes.cast(out, ctypes.c_void_p)) != 0:
+        raise ValueError(f"gemm_route: the launch rejects {m} x {n} x {k} ({dtype}, {emode}, {amode}) or rr_set_tuning "
+                         f"rejects {tuple(tune)}")
+    return GemmRoute(*out)
+
+
 def stem_pool_h2(x, x_amax, wc, bias, stride=2, pad=3, y_amax=None):
     """The NHWC4 stem conv + bias + ReLU with the 3x3/2 padding-1 max-pool
     fused (rr_stem_pool_h2): [B,H,W,4] -> pooled [B,PH,PW,64], the same bits
@@ -969,14 +1008,8 @@ def topk_merge(part_scores, part_idx, k_out):
     return os_, oi
 
 
-_TUNE_KEYS = {"gemm_cfg": _lib.TUNE_GEMM_CFG, "gemm_bk": _lib.TUNE_GEMM_BK, "lp_cfg": _lib.TUNE_LP_CFG,
-              "s3_cfg": _lib.TUNE_S3_CFG, "s3_stagger": _lib.TUNE_S3_STAGGER, "sweep_mf16": _lib.TUNE_SWEEP_MF16,
-              "sweep_il": _lib.TUNE_SWEEP_IL, "conv_il": _lib.TUNE_CONV_IL,
-              "halo_mf": _lib.TUNE_HALO_MF, "s3_cfg_res": _lib.TUNE_S3_CFG_RES,
-              "sweep_form": _lib.TUNE_SWEEP_FORM, "halo_2d": _lib.TUNE_HALO_2D,
-              "trunk_parts": _lib.TUNE_TRUNK_PARTS}
-_TUNE_DEFAULT = {"s3_stagger": -1, "sweep_mf16": -1, "sweep_il": -1, "conv_il": -1, "halo_mf": -1,
-                 "sweep_form": -1, "halo_2d": -1, "trunk_parts": -1}  # the library's own pick (0 elsewhere)
+_TUNE_KEYS = {name: key for name, (key, _) in _lib.TUNING.items()}
+_TUNE_DEFAULT = {name: default for name, (_, default) in _lib.TUNING.items()}  # the library's own pick
 
 
 class tuning:
@@ -999,7 +1032,7 @@ class tuning:
 
     def __exit__(self, *exc):
         for k in self.kw:
-            _lib.lib().rr_set_tuning(self.h, _TUNE_KEYS[k], _TUNE_DEFAULT.get(k, 0))
+            _lib.lib().rr_set_tuning(self.h, _TUNE_KEYS[k], _TUNE_DEFAULT[k])
         return False
 
 

@@ -19,6 +19,14 @@ def test_header_matches_binding_table():
     assert header_symbols() == sorted(_lib.SIGNATURES)
 
 
+def test_abi_version_in_one_place():
+    """The ABI revision: the library's, the binding's, the header's #define and
+    the number this suite was written against are one number."""
+    txt = open(os.path.join(ROOT, "include", "rr.h")).read()
+    defined = int(re.search(r"^#define RR_ABI_VERSION (\d+)$", txt, flags=re.M).group(1))
+    assert _lib.lib().rr_abi_version() == _lib.ABI_VERSION == defined == 9
+
+
 def test_library_exports_all_symbols():
     L = ctypes.CDLL(_lib.LIB_PATH)
     for name in header_symbols():

@@ -192,7 +192,7 @@ def test_bf16_linear_ragged_shapes_every_config(cuda, cfg, shape):
 def test_bf16_linear_persistent_tile_boundary(cuda, shape):
     """N = 256 / 512 at K = 320, one ragged row tile (M = 1) and fewer tiles
     than blocks (M = 257): the default (the persistent k-stream of
-    gemm_lpp.hip for its flag sets: bias -> bf16, bias + residual -> fp32,
+    gemm_lpp.hip, at K = 320 its three-A-stage form, for its flag sets: bias -> bf16, bias + residual -> fp32,
     bias + QuickGELU -> bf16) and the one-tile kernel (lp_cfg 3) both meet
     the float64 bar on every flag set and output type, and agree bit for bit
     on the persistent kernel's flag sets."""

@@ -293,9 +293,10 @@ def test_nan_rank_last_prefilter_every_sweep(cuda, nq, d, tune):
     after every number, by index; the NaN query returns 0..k-1; k > #rows pads
     with (-inf, -1)) for the exact prefilter ranker under every bf16 filter
     sweep.  Which kernel runs pass 2 (and, for the gemm core's configs, the
-    seed scores) is read off launch_lp / launch_lp_cfg in csrc/gemm_lp.hip:
+    seed scores) is gemm_route's answer (csrc/gemm_route.hpp), asserted for these
+    parameter sets in tests/test_gemm_route.py::test_claims_of_the_gpu_tests:
 
-    * sweep_form 0 at the default lp_cfg: pick_lp's cost model gives the
+    * sweep_form 0 at the default lp_cfg: the cost model (lp_pick_cfg) gives the
       128x128 tile of gemm_lp_kernel (16x16x32 bf16 MFMA) at both (6, 128) and
       (256, 256) over 20000 rows;
     * sweep_form 1: sweep128_kernel of csrc/sweep16.hip (128-B LDS rows, K %
@@ -303,7 +304,7 @@ def test_nan_rank_last_prefilter_every_sweep(cuda, nq, d, tune):
       nq = 256 leaves 64 of the tile's 320 query columns as padding, whose
       threshold is +inf;
     * lp_cfg 3: gemm_lp_kernel's 8-wave 256x256 tile (LDS-DMA, K % 64 == 0);
-      lp_cfg 4: its 256x320 tile on 32x32x16 MFMA (launch_t1<4, 2, 2, 5>),
+      lp_cfg 4: its 256x320 tile on 32x32x16 MFMA (<4, 2, 2, 5>),
       by default with the next k-tile's DMA spread among the MFMAs; sweep_il 0:
       as one burst; sweep_mf16 1: the tile's 16x16x32 form, with either DMA
       issue; lp_cfg 2: the 4-wave 256x64 tile.  These four run 33 queries
@@ -346,8 +347,8 @@ def test_nan_rank_last_exact_every_f32_tile(cuda, cfg, bk):
     ("fp8", 256, 256, dict(lp_cfg=5)), ("fp8", 33, 384, dict(lp_cfg=2)),
 ], ids=lambda v: "-".join(f"{a}{b}" for a, b in v.items()) if isinstance(v, dict) else str(v))
 def test_nan_rank_last_lowp_every_sweep(cuda, dtype, nq, d, tune):
-    """NaN rows and a NaN query through rr_cosine_topk_lp.  Kernels (launch_lp
-    in csrc/gemm_lp.hip): bf16 takes the same sweeps as the prefilter's pass 2
+    """NaN rows and a NaN query through rr_cosine_topk_lp.  Kernels (gemm_route,
+    asserted in tests/test_gemm_route.py): bf16 takes the same sweeps as the prefilter's pass 2
     (sweep_form 0 + lp_cfg 0: gemm_lp_kernel's 128x128 tile; sweep_form 1 / 2:
     sweep128_kernel / sweep16_kernel<8> of csrc/sweep16.hip; lp_cfg 5: the
     8-phase bf16 pipeline of csrc/gemm_8p.hip, K % 128 == 0).  fp8 has no

@@ -76,7 +76,6 @@ def test_symbols_and_abi():
     for name in NEW_SYMBOLS:
         assert hasattr(L, name) and name in _lib.SIGNATURES
     L = _lib.lib()
-    assert L.rr_abi_version() == 8 == _lib.ABI_VERSION
     lv = (ctypes.c_int * 3)(1, 2, 4)
     assert L.rr_spp_max(None, None, 1, 7, 7, 4, ctypes.cast(lv, ctypes.c_void_p), 3, None, None) == _lib.RR_EINVAL
     assert L.rr_spoc_refine(None, None, None, 1, 4, 32, None, 0.0, None, None, None, None, None) == _lib.RR_EINVAL

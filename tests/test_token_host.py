@@ -64,7 +64,6 @@ def test_symbols_and_abi():
     for name in ("rr_attention_hd128", "rr_token_pool", "rr_gelu"):
         assert hasattr(L, name) and name in _lib.SIGNATURES
     L = _lib.lib()
-    assert L.rr_abi_version() == 8 == _lib.ABI_VERSION
     assert L.rr_attention_hd128(None, None, 128, None, 128, None, 128, 1, 1, 1, 1, None, None) == _lib.RR_EINVAL
     assert L.rr_token_pool(None, None, 1, 1, 256, None, 1, None, None) == _lib.RR_EINVAL
     assert L.rr_gelu(None, None, 1, None, None) == _lib.RR_EINVAL
