@@ -75,7 +75,8 @@ typedef struct rr_handle_s* rr_handle_t;
  * rr_cls_attn_pool and rr_linear_splitk_ex (the token aggregator's folded last
  * layer: added, no existing entry changed), rr_spp_regions, rr_spp_max,
  * rr_spoc_refine and rr_linear_groupmax (the SpoC head: added, no existing
- * entry changed), and the native
+ * entry changed), rr_se_squeeze and rr_se_apply (the SE-ResNet trunk's gate:
+ * added, no existing entry changed), and the native
  * trunk plan's rr_trunk_h2_* entries, rr_timing_collect_ex and the tuning key
  * RR_TUNE_TRUNK_PARTS (16); rr_timing_collect keeps its arguments and now
  * returns the UNION of the class's launch intervals (equal to the former sum
@@ -955,6 +956,51 @@ int rr_spoc_refine(rr_handle_t h, const float* u, const float* ctx, int m,
 int rr_linear_groupmax(rr_handle_t h, const float* x, int b, int r, int k,
                        const float* w, const float* bias, int n, int act,
                        float* out, void* stream);
+
+/* ---- Squeeze-and-Excitation block (models/senet_g2.py) ------------------- */
+/* The squeeze: mean[i][ch] = (1 / hw) sum_p y[i][p][ch], y [b][hw][c] NHWC
+ * fp32 (conv3 + bn3's output), mean [b][c].  Replaces SEBlock's
+ * AdaptiveAvgPool2d(1) (:17, :27).  Values are signed and nothing is clamped
+ * (rr_gem_pool clamps at eps, so it cannot serve).  One pass over y with 16-B
+ * loads along c: a workgroup takes a chunk of an image's positions and one
+ * 256-channel group; an image's positions are split over workgroups only
+ * while whole images leave the chip short of work, by a rule of (b, hw)
+ * alone, the chunks' partial sums pass through the heads' per-stream scratch
+ * and are added in a fixed order, then divided by hw: no float atomics, the
+ * same bits on every run and on every stream.
+ * c % 256 == 0 (the fixed-order adder's row length; every bottleneck output
+ * width is one), hw >= 1, b >= 0; y and mean 16-B aligned (else RR_EINVAL,
+ * nothing written); b == 0 is RR_OK and launches nothing; offsets are 64-bit.
+ * Timing class 3.                                                           */
+int rr_se_squeeze(rr_handle_t h, const float* y, int b, int hw, int c,
+                  float* mean, void* stream);
+
+/* The excitation's second FC, the scale, the identity and the ReLU:
+ *   g[i][ch]       = sigmoid(w2[ch][:] . hidden[i][:])
+ *   out[i][p][ch]  = act(y[i][p][ch] * g[i][ch] + identity[i][p][ch])
+ * w2 [c][cr] (fc.2.weight), hidden [b][cr] = relu(W1 mean) (from
+ * rr_linear_splitk, act 1), y / identity / out [b][hw][c]; act is max(0, .)
+ * when relu != 0.  Replaces SEBlock's fc[2], fc[3] and x * y.expand_as(x)
+ * (:21-22, :28-29) and SEBottleneck's out += residual; relu (:69-70).
+ * identity may be NULL (no add).  gate_out [b][c] (may be NULL) receives the
+ * g.  out_amax (may be NULL; RR_AMAX_SLOTS words zeroed by the caller)
+ * receives max |out| over the finite values, in the record format of
+ * rr_conv2d_h2's y_amax: the next block's convs read it and need no extra
+ * pass.  out may alias y or identity: each element is read and written by the
+ * same thread.
+ * A workgroup owns one (image, 64-channel slab, row chunk): it forms its 64
+ * gates once from the w2 slab (64 x cr floats) in an order fixed by cr alone,
+ * so every row chunk of an image applies the same gate bits and an image's
+ * gates are the same bits alone or in a batch, then streams its rows with
+ * 16-B loads and stores.  The sigmoid is 1 / (1 + exp(-z)): exactly 0 / 1 at
+ * logits of -100 / +100, never NaN for a finite logit.
+ * c % 64 == 0; cr % 4 == 0, 4 <= cr <= 512; hw >= 1; b >= 0; every pointer
+ * 16-B aligned (else RR_EINVAL, nothing written); b == 0 is RR_OK and
+ * launches nothing; offsets are 64-bit.  Timing class 3.                    */
+int rr_se_apply(rr_handle_t h, const float* y, const float* hidden,
+                const float* w2, const float* identity, int b, int hw, int c,
+                int cr, int relu, float* gate_out, float* out,
+                unsigned* out_amax, void* stream);
 
 /* ---- native ResNet trunk plan (f16x2 core) -------------------------------
  * One call per forward for the whole bottleneck-ResNet trunk (torchvision

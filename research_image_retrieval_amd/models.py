@@ -19,6 +19,11 @@ SpoC (models/spoc.py:97-248) likewise: ``get_spoc_model(num_classes,
 backbone=..., pyramid_levels=..., context_dim=..., use_context=...)`` or
 ``SpoCWrapper``; ``get_model('spoc_r50' | 'spoc_r101', ...)`` still raises
 NotImplementedError.
+SENet-G2+ (models/senet_g2.py:12-274), the one method on an SE-ResNet trunk
+(networks.SENet), likewise: ``get_senet_g2_model(num_classes, backbone='senet50'
+| 'senet101', reduction=..., gem_p=...)`` or ``SENetG2Wrapper``;
+``get_model('senet_g2_50' | 'senet_g2_101', ...)`` still raises
+NotImplementedError.
 Training (``forward(x, targets)`` losses, optimizers) is out of scope
 (SURVEY.md §2 row 13): ``forward`` only produces eval-mode logits.
 """
@@ -26,7 +31,7 @@ import torch
 
 from . import ops
 from . import weights as W
-from .networks import ResNet, HeadConv, _Extractor, EPS_L2
+from .networks import ResNet, SENet, HeadConv, _Extractor, EPS_L2
 
 
 class _TrunkHeadModel(_Extractor):
@@ -55,13 +60,18 @@ class _TrunkHeadModel(_Extractor):
         """from_sd of the state dict, or of synthetic(seed + 1, *args) when there is none."""
         return from_sd(synthetic(seed + 1, *args) if state_dict is None else state_dict)
 
+    def _make_trunk(self, backbone, state_dict, seed, device, conv_math, stride_on):
+        """The trunk _build puts in self.backbone: a networks.ResNet, unless a
+        subclass builds another class with ResNet.maps' contract."""
+        return ResNet(backbone, state_dict, seed, device, conv_math=conv_math, stride_on=stride_on)
+
     def _build(self, head, fit, backbone, state_dict, seed, device, conv_math, stride_on):
         """The trunk, then the head's tensors on its device.  fit: (key, the
         reference's name) of the head weight whose columns are the trunk's
         channels, or None."""
         self.device = torch.device(device)
         self.conv_math = conv_math
-        self.backbone = ResNet(backbone, state_dict, seed, device, conv_math=conv_math, stride_on=stride_on)
+        self.backbone = self._make_trunk(backbone, state_dict, seed, device, conv_math, stride_on)
         if fit is not None and head[fit[0]].shape[1] != self.backbone.outputdim_block5:
             raise ValueError(f"{type(self).__name__}: {fit[1]} does not fit the trunk")
         self.w = {k: v.to(self.device) for k, v in head.items()}
@@ -630,6 +640,75 @@ class TokenWrapper(_Wrapper):
 
 def get_token_model(num_classes, backbone="resnet50", **kwargs):
     return TokenWrapper(num_classes=num_classes, backbone=backbone, **kwargs)
+
+
+class SENetG2Model(_TrunkHeadModel):
+    """models/senet_g2.py:156-213, eval mode: the SE-ResNet trunk
+    (networks.SENet) -> G2Pooling (:132-153: GeM with a learnable p, then
+    alpha * g + beta) -> feature_proj Linear(2048, feature_dim);
+    extract_descriptor adds F.normalize.
+
+    Launches after the trunk: rr_gem_pool with p read from g2_pool.p (eps
+    1e-6), one rr_linear with alpha and beta folded into the projection on the
+    host (weights.senet_g2_fold: W' = alpha W, b' = b + beta W 1, float64,
+    rounded once), rr_l2_normalize.
+
+    Constructor: the reference's (layers, num_classes, feature_dim, reduction,
+    gem_p), then state_dict (trunk keys as networks.SENet accepts, head keys as
+    weights.senet_g2_head_from_state_dict; at the wrapper's level, the model's,
+    or either under ``module.``), seed (synthetic weights when state_dict is
+    None), device and conv_math as GeMModel.  layers: (3, 4, 6, 3) or (3, 4, 23,
+    3), or the backbone's name "senet50" / "senet101".  There is no pretrained
+    argument: the reference's SENet is randomly initialised (:93-99).
+
+    get_model("senet_g2_50" | "senet_g2_101") still raises NotImplementedError:
+    the names stay in OUT_OF_SCOPE and out of MODEL_REGISTRY (build the model
+    with get_senet_g2_model)."""
+
+    _LAYERS = {(3, 4, 6, 3): "senet50", (3, 4, 23, 3): "senet101"}
+
+    def __init__(self, layers=(3, 4, 6, 3), num_classes=1000, feature_dim=2048, reduction=16, gem_p=3.0,
+                 state_dict=None, seed=0, device="cuda", conv_math="h2"):
+        name = layers if isinstance(layers, str) else self._LAYERS.get(tuple(int(v) for v in layers))
+        if name not in W.SENET_TRUNKS:
+            raise ValueError(f"Unsupported backbone: {layers}")
+        self.reduction = W.senet_check_reduction(reduction)
+        head = self._load_head(state_dict, seed, W.senet_g2_head_from_state_dict, W.synthetic_senet_g2_head,
+                               num_classes, feature_dim, gem_p)
+        if head["proj_w"].shape[0] != feature_dim:
+            raise ValueError("SENetG2Model: head weight shapes do not fit feature_dim")
+        # python floats, read before any device work
+        self.p, self.alpha, self.beta = (head.pop(k) for k in ("p", "alpha", "beta"))
+        self._build(head, ("proj_w", "feature_proj"), name, state_dict, seed, device, conv_math, "3x3")
+        self.feature_dim = feature_dim
+        self.outputdim = feature_dim
+
+    def _make_trunk(self, backbone, state_dict, seed, device, conv_math, stride_on):
+        return SENet(backbone, state_dict, seed, device, conv_math=conv_math, reduction=self.reduction)
+
+    def head(self, x4, x4_amax=None, taps=None):
+        """x4 NHWC -> features [B,feature_dim] (:179-191).  taps: a dict that
+        receives pooled [B,2048] (the GeM before alpha and beta) and features
+        (tests)."""
+        pooled = ops.gem_pool(x4, self.p, 1e-6)
+        f = ops.linear(pooled, self.w["proj_wf"], self.w["proj_bf"])
+        if taps is not None:
+            taps.update(pooled=pooled, features=f)
+        return f
+
+
+class SENetG2Wrapper(_Wrapper):
+    """models/senet_g2.py:216-251: training-loop facade over SENetG2Model."""
+
+    def __init__(self, num_classes, backbone="senet50", feature_dim=2048, reduction=16, gem_p=3.0, **kw):
+        if backbone not in W.SENET_TRUNKS:
+            raise ValueError(f"Unsupported backbone: {backbone}")
+        super().__init__(SENetG2Model(layers=backbone, num_classes=num_classes, feature_dim=feature_dim,
+                                      reduction=reduction, gem_p=gem_p, **kw))
+
+
+def get_senet_g2_model(num_classes, backbone="senet50", **kwargs):
+    return SENetG2Wrapper(num_classes=num_classes, backbone=backbone, **kwargs)
 
 
 MODEL_REGISTRY = {

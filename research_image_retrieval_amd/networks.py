@@ -21,6 +21,38 @@ def _check_conv_math(conv_math):
         raise ValueError("conv_math must be 'h2' or 'f32'")
 
 
+def _load_trunk_convs(net, sd, arch, device, conv_math):
+    """What the bottleneck trunks' constructors share: the torchvision-keyed
+    convs of sd (arch: a weights.RESNET_LAYERS name) with their BNs folded, on
+    the device in net.convs, the stem padded to 4 input channels; on the f16x2
+    core the split weights in net.convs_h2."""
+    net.device = torch.device(device)
+    folded = W.folded_resnet(sd, arch)
+    # stem weights padded to 4 input channels (zero) for the NHWC4 tap path
+    w1, b1 = folded["conv1"]
+    folded["conv1"] = (torch.nn.functional.pad(w1, (0, 1)).contiguous(), b1)
+    net.convs = {k: (w.to(net.device), b.to(net.device)) for k, (w, b) in folded.items()}
+    net.layers = W.RESNET_LAYERS[arch]
+    net.conv_math = conv_math
+    net.convs_h2 = {}
+    if conv_math == "h2":
+        net.convs_h2 = {k: ops.H2Conv(w) for k, (w, _) in net.convs.items()}
+        # the stem conv + ReLU + max-pool as one launch (ops.stem_pool_h2)
+        net.fuse_stem_pool = True
+
+
+def _stem_h2(net, x, rec):
+    """The f16x2 stem of a bottleneck trunk: x's record into rec[0], then the
+    stem conv, its ReLU and the max-pool (one launch where net.fuse_stem_pool
+    and the stem has 64 channels), the output's record in rec[1]."""
+    cv, h2 = net.convs, net.convs_h2
+    ops.amax_f32(x, rec[0])
+    if net.fuse_stem_pool and h2["conv1"].cout == 64:
+        return ops.stem_pool_h2(x, rec[0], h2["conv1"], cv["conv1"][1], 2, 3, rec[1])
+    x = ops.conv2d_h2(x, rec[0], h2["conv1"], cv["conv1"][1], 2, 3, None, True, rec[1])
+    return ops.maxpool2d(x, 3, 2, 1)
+
+
 class ResNet:
     """torchvision resnet children[:-2] trunk (networks/backbone.py:60-109:
     block1 = conv1/bn1/relu/maxpool, block2..5 = layer1..4), NHWC, BN folded.
@@ -52,21 +84,10 @@ class ResNet:
             raise ValueError(f"Unsupported or unknown architecture: {name}!")
         self.name = name
         sd = W.synthetic_resnet_state_dict(name, seed) if state_dict is None else W.to_torchvision_keys(state_dict)
-        self.device = torch.device(device)
-        folded = W.folded_resnet(sd, name)
-        # stem weights padded to 4 input channels (zero) for the NHWC4 tap path
-        w1, b1 = folded["conv1"]
-        folded["conv1"] = (torch.nn.functional.pad(w1, (0, 1)).contiguous(), b1)
-        self.convs = {k: (w.to(self.device), b.to(self.device)) for k, (w, b) in folded.items()}
-        self.layers = W.RESNET_LAYERS[name]
-        self.conv_math = conv_math
-        self.convs_h2 = {}
+        _load_trunk_convs(self, sd, name, device, conv_math)
         if conv_math == "h2":
-            self.convs_h2 = {k: ops.H2Conv(w) for k, (w, _) in self.convs.items()}
             # each stage's first block: conv3 + downsample as one GEMM (ops.H2Bottleneck)
             self.fuse_downsample = True
-            # the stem conv + ReLU + max-pool as one launch (ops.stem_pool_h2)
-            self.fuse_stem_pool = True
             self.bneck_h2 = {}
             for li in range(len(self.layers)):
                 p = f"layer{li + 1}.0"
@@ -105,12 +126,7 @@ class ResNet:
         cv, h2 = self.convs, self.convs_h2
         hook = hook or (lambda i: None)
         rec = ops.amax_records(2 + 3 * sum(self.layers), x.device)
-        ops.amax_f32(x, rec[0])
-        if self.fuse_stem_pool and h2["conv1"].cout == 64:
-            x = ops.stem_pool_h2(x, rec[0], h2["conv1"], cv["conv1"][1], 2, 3, rec[1])
-        else:
-            x = ops.conv2d_h2(x, rec[0], h2["conv1"], cv["conv1"][1], 2, 3, None, True, rec[1])
-            x = ops.maxpool2d(x, 3, 2, 1)
+        x = _stem_h2(self, x, rec)
         hook(0)
         xa, r, x3, x3a, ci = rec[1], 2, None, None, 1
         for li, nb in enumerate(self.layers):
@@ -180,6 +196,109 @@ class ResNet:
             ret += (x4a,)
         return ret if len(ret) > 1 else x4
 
+    __call__ = forward
+
+
+class SENet:
+    """The SE-ResNet trunk of models/senet_g2.py:32-129 (SEBottleneck, SENet),
+    NHWC, BN folded: torchvision-v1.5 bottlenecks (the stride on the 3x3, :41)
+    whose conv3 + bn3 output is gated per channel by a Squeeze-and-Excitation
+    block (:12-29) before the identity is added.  name: "senet50" = (3, 4, 6,
+    3) or "senet101" = (3, 4, 23, 3); reduction: the SE blocks' (default 16).
+
+    maps() has ResNet.maps' contract.  Launches per block: conv1, conv2, conv3
+    WITHOUT residual, ReLU or record (a stage's first block: its downsample
+    projection as a separate conv before them; no fused conv3 + downsample
+    GEMM, whose epilogue cannot gate one half of its sum), then
+    ops.se_squeeze, ops.linear_splitk (fc.0 + ReLU) and ops.se_apply in place
+    on conv3's output (fc.2, the sigmoid, the scale, the identity, the ReLU),
+    which on the f16x2 core publishes the block's max-|x| record for the next
+    block's convs.  There is no plan(): the native trunk plan knows no SE
+    block.
+
+    state_dict: conv / BN keys as ResNet accepts them, plus
+    layerN.M.se.fc.{0,2}.weight (weights.senet_se_from_state_dict); None: the
+    seeded weights.synthetic_senet_state_dict."""
+
+    outputdim_block5 = 2048
+    outputdim_block4 = 1024
+
+    def __init__(self, name="senet50", state_dict=None, seed=0, device="cuda", conv_math="h2", reduction=16):
+        _check_conv_math(conv_math)
+        if name not in W.SENET_TRUNKS:
+            raise ValueError(f"Unsupported backbone: {name}")
+        self.name = name
+        self.reduction = W.senet_check_reduction(reduction)
+        sd = W.synthetic_senet_state_dict(name, seed, reduction) if state_dict is None else state_dict
+        se = W.senet_se_from_state_dict(sd, name, reduction)
+        _load_trunk_convs(self, W.to_torchvision_keys(sd), W.SENET_TRUNKS[name], device, conv_math)
+        self.se = {p: (w1.to(self.device), w2.to(self.device)) for p, (w1, w2) in se.items()}
+
+    def _conv(self, x, xa, name, stride, pad, relu, ya=None):
+        """One folded conv on the trunk's core (xa / ya: the input's and the
+        output's max-|x| record, read by the f16x2 core alone)."""
+        w, b = self.convs[name]
+        if self.conv_math == "h2":
+            return ops.conv2d_h2(x, xa, self.convs_h2[name], b, stride, pad, None, relu, ya)
+        return ops.conv2d(x, w, b, stride, pad, None, relu)
+
+    def block(self, x, xa, p, entry, stride, rec=None, hook=None, ci=0, taps=None):
+        """SEBottleneck.forward (:51-72) for block p on x (record xa): entry =
+        the block has a downsample projection, stride = the 3x3's.  rec: three
+        zeroed records (conv1's output, conv2's, the block's) on the f16x2
+        core, None on "f32".  taps: a dict that receives mean, hidden and gate
+        (tests).  Returns the block's output; its record is rec[2]."""
+        r0, r1, r2 = rec if rec is not None else (None, None, None)
+        hook = hook or (lambda i: None)
+        idn = self._conv(x, xa, f"{p}.downsample.0", stride, 0, False) if entry else x
+        y = self._conv(x, xa, f"{p}.conv1", 1, 0, True, r0)
+        hook(ci)
+        y = self._conv(y, r0, f"{p}.conv2", stride, 1, True, r1)
+        hook(ci + 1)
+        y = self._conv(y, r1, f"{p}.conv3", 1, 0, False)
+        hook(ci + 2)
+        w1, w2 = self.se[p]
+        mean = ops.se_squeeze(y)
+        hidden = ops.linear_splitk(mean, w1, None, act=1)
+        got = ops.se_apply(y, hidden, w2, idn, relu=True, want_gate=taps is not None, out=y, out_amax=r2)
+        if taps is not None:
+            taps.update(mean=mean, hidden=hidden, gate=got[1])
+            return got[0]
+        return got
+
+    def maps(self, x, hook=None, want_x3=False, taps=None):
+        """ResNet.maps' contract: NHWC fp32 pixels (3 or 4 channels) -> (x3, x4,
+        x3_amax, x4_amax), records None on the "f32" trunk.  taps: a dict that
+        receives {block prefix: {mean, hidden, gate}} (tests)."""
+        if x.shape[-1] == 3:
+            x = torch.nn.functional.pad(x, (0, 1))
+        x = x.contiguous()
+        h2 = self.conv_math == "h2"
+        hook = hook or (lambda i: None)
+        rec, xa = None, None
+        if h2:
+            rec = ops.amax_records(2 + 3 * sum(self.layers), x.device)
+            x = _stem_h2(self, x, rec)
+            hook(0)
+            xa = rec[1]
+        else:
+            w, b = self.convs["conv1"]
+            x = ops.maxpool2d(ops.conv2d(x, w, b, 2, 3, None, True), 3, 2, 1)
+        r, ci, x3, x3a = 2, 1, None, None
+        for li, nb in enumerate(self.layers):
+            for bi in range(nb):
+                p = f"layer{li + 1}.{bi}"
+                t = None if taps is None else taps.setdefault(p, {})
+                x = self.block(x, xa, p, bi == 0, 2 if (bi == 0 and li > 0) else 1, rec[r:r + 3] if h2 else None,
+                               hook if h2 else None, ci, t)
+                if h2:
+                    xa = rec[r + 2]
+                r, ci = r + 3, ci + 3
+            if li == 2:
+                x3, x3a = x, xa
+        return (x3, x, x3a, xa) if want_x3 else (None, x, None, xa)
+
+    forward = ResNet.forward
     __call__ = forward
 
 

@@ -878,6 +878,75 @@ def linear_groupmax(x, w, bias, act=0):
     return out
 
 
+def se_squeeze(y_nhwc):
+    """The SE block's squeeze (rr_se_squeeze): y NHWC [B,H,W,C] (or [B,HW,C]),
+    signed, C % 256 == 0 -> the per-channel spatial mean [B,C]."""
+    _f32(y_nhwc, "se_squeeze y")
+    if y_nhwc.dim() not in (3, 4):
+        raise ValueError(f"se_squeeze: y [B,H,W,C] or [B,HW,C], got {tuple(y_nhwc.shape)}")
+    b, c = y_nhwc.shape[0], y_nhwc.shape[-1]
+    if c % 256 or c == 0:
+        raise ValueError("se_squeeze: c % 256 == 0, c > 0")
+    hw = 1
+    for v in y_nhwc.shape[1:-1]:
+        hw *= v
+    if hw < 1:
+        raise ValueError("se_squeeze: at least one position per image")
+    dev = _dev(y_nhwc)
+    out = torch.empty((b, c), dtype=torch.float32, device=y_nhwc.device)
+    if b:
+        hd = _lib.handle(dev)
+        _lib.check(_lib.lib().rr_se_squeeze(hd, _ptr(y_nhwc), b, hw, c, _ptr(out), _stream(dev)), hd, "rr_se_squeeze")
+    return out
+
+
+def se_apply(y, hidden, w2, identity=None, relu=True, want_gate=False, out=None, out_amax=None):
+    """The SE block's gate, identity add and ReLU (rr_se_apply): y NHWC
+    [B,H,W,C] (or [B,HW,C]), hidden [B,CR] = relu(W1 mean), w2 [C,CR] ->
+    act(y * sigmoid(hidden @ w2.T)[:, None, :] + identity), shaped as y, and the
+    gates [B,C] as a second value with want_gate.  C % 64 == 0, CR % 4 == 0,
+    4 <= CR <= 512.  identity: None or a tensor shaped as y.  out: None (a new
+    tensor), y or identity (in place).  out_amax: a zeroed record that receives
+    max |out| (as conv2d_h2's y_amax)."""
+    _f32(y, "se_apply y")
+    _f32(hidden, "se_apply hidden")
+    _f32(w2, "se_apply w2")
+    if y.dim() not in (3, 4) or hidden.dim() != 2 or w2.dim() != 2:
+        raise ValueError(f"se_apply: y [B,H,W,C], hidden [B,CR] and w2 [C,CR], got {tuple(y.shape)}, "
+                         f"{tuple(hidden.shape)} and {tuple(w2.shape)}")
+    b, c = y.shape[0], y.shape[-1]
+    cr = hidden.shape[1]
+    if c % 64 or c == 0:
+        raise ValueError("se_apply: c % 64 == 0, c > 0")
+    if cr % 4 or not 4 <= cr <= 512:
+        raise ValueError("se_apply: cr % 4 == 0, 4 <= cr <= 512")
+    if hidden.shape[0] != b or tuple(w2.shape) != (c, cr):
+        raise ValueError(f"se_apply: hidden [{b},{cr}] and w2 [{c},{cr}], got {tuple(hidden.shape)} and "
+                         f"{tuple(w2.shape)}")
+    hw = 1
+    for v in y.shape[1:-1]:
+        hw *= v
+    if hw < 1:
+        raise ValueError("se_apply: at least one position per image")
+    if identity is not None and tuple(_f32(identity, "se_apply identity").shape) != tuple(y.shape):
+        raise ValueError("se_apply: identity must be shaped as y")
+    if out is not None and out is not y and out is not identity:
+        raise ValueError("se_apply: out must be None, y or identity")
+    if out_amax is not None and (out_amax.dtype != torch.int32 or out_amax.numel() != AMAX_SLOTS or
+                                 not out_amax.is_contiguous()):
+        raise ValueError("se_apply: out_amax must be a contiguous int32 [RR_AMAX_SLOTS] record")
+    if any(t is not None and t.device != y.device for t in (hidden, w2, identity, out_amax)):
+        raise ValueError("se_apply: every tensor must be on one device")
+    dev = _dev(y)
+    o = torch.empty_like(y) if out is None else out
+    gate = torch.empty((b, c), dtype=torch.float32, device=y.device) if want_gate else None
+    if b:
+        hd = _lib.handle(dev)
+        _lib.check(_lib.lib().rr_se_apply(hd, _ptr(y), _ptr(hidden), _ptr(w2), _ptr(identity), b, hw, c, cr, int(bool(relu)),
+                                          _ptr(gate), _ptr(o), _ptr(out_amax), _stream(dev)), hd, "rr_se_apply")
+    return (o, gate) if want_gate else o
+
+
 def gelu(x, out=None):
     """Exact (erf) GELU (rr_gelu), elementwise; out=x runs in place."""
     _f32(x, "gelu")

@@ -1002,6 +1002,124 @@ def folded_resnet(sd, arch):
     return out
 
 
+# ---- SE-ResNet trunk (models/senet_g2.py:12-129) ----------------------------
+# SENet's conv / BN keys are torchvision's (downsample in layer1.0 included), so
+# to_torchvision_keys and folded_resnet serve under the matching resnet name;
+# each bottleneck adds se.fc.0.weight [c / r, c] and se.fc.2.weight [c, c / r].
+SENET_TRUNKS = {"senet50": "resnet50", "senet101": "resnet101"}
+SENET_SE_GAIN = 8.0  # synthetic_senet_state_dict: the SE weights' gain over N(0, 1 / fan_in)
+
+
+def senet_block_names(arch):
+    """(block prefix, output channels) of every SE bottleneck, in forward order."""
+    if arch not in SENET_TRUNKS:
+        raise ValueError(f"Unsupported backbone: {arch}")
+    return [(f"layer{li + 1}.{bi}", 256 << li) for li, nb in enumerate(RESNET_LAYERS[SENET_TRUNKS[arch]])
+            for bi in range(nb)]
+
+
+def senet_check_reduction(reduction):
+    """The hidden widths c // reduction of the four stages must suit rr_se_apply
+    (cr % 4 == 0, 4 <= cr <= 512): reductions 4, 8, 16, 32 and 64 do."""
+    if not isinstance(reduction, int) or isinstance(reduction, bool) or reduction < 1:
+        raise ValueError(f"SENet: reduction must be a positive int, got {reduction!r}")
+    for c in (256, 512, 1024, 2048):
+        cr = c // reduction
+        if c % reduction or cr % 4 or not 4 <= cr <= 512:
+            raise ValueError(f"SENet: reduction {reduction} gives a hidden width of {c}/{reduction} at {c} channels; "
+                             "rr_se_apply needs a multiple of 4 in 4..512")
+    return reduction
+
+
+def senet_se_from_state_dict(sd, arch, reduction=16):
+    """The SE weights of a checkpoint (keys as to_torchvision_keys accepts the
+    trunk's) -> {block prefix: (w1 [c / r, c], w2 [c, c / r])} fp32 contiguous;
+    ValueError naming the key for a missing or mis-shaped weight."""
+    senet_check_reduction(reduction)
+    tv = to_torchvision_keys(sd)
+    out = collections.OrderedDict()
+    for p, c in senet_block_names(arch):
+        ws = []
+        for i, shape in (("0", (c // reduction, c)), ("2", (c, c // reduction))):
+            k = f"{p}.se.fc.{i}.weight"
+            if k not in tv:
+                raise ValueError(f"SENet: missing key {k}")
+            if tuple(tv[k].shape) != shape:
+                raise ValueError(f"{k}: expected {shape}, got {tuple(tv[k].shape)}")
+            ws.append(_f(tv[k]))
+        out[p] = tuple(ws)
+    return out
+
+
+def synthetic_senet_state_dict(arch="senet50", seed=0, reduction=16):
+    """synthetic_resnet_state_dict of the matching resnet plus, from a second
+    stream seeded [seed, 1], every block's se.fc.0 / se.fc.2 weights drawn
+    N(0, 1) * SENET_SE_GAIN / sqrt(fan_in).  With PyTorch's default init every
+    gate sits within 0.49-0.51, and a gate computed from the wrong hidden
+    column would pass any test; at gain 8 every block's gates span
+    [<= 0.2, >= 0.8] on the trunk fixture's inputs (make_golden_senet.py
+    asserts it) without saturating."""
+    senet_check_reduction(reduction)
+    blocks = senet_block_names(arch)
+    sd = synthetic_resnet_state_dict(SENET_TRUNKS[arch], seed)
+    rs = np.random.RandomState([seed, 1])
+    for p, c in blocks:
+        cr = c // reduction
+        sd[f"{p}.se.fc.0.weight"] = _t(rs.standard_normal((cr, c)) * (SENET_SE_GAIN / np.sqrt(c)))
+        sd[f"{p}.se.fc.2.weight"] = _t(rs.standard_normal((c, cr)) * (SENET_SE_GAIN / np.sqrt(cr)))
+    return sd
+
+
+SENET_G2_HEAD_KEYS = ("g2_pool.p", "g2_pool.alpha", "g2_pool.beta", "feature_proj.weight", "feature_proj.bias",
+                      "classifier.weight", "classifier.bias")
+
+
+def senet_g2_fold(proj_w, proj_b, alpha, beta):
+    """G2+'s alpha * g + beta (models/senet_g2.py:151) folded into the
+    projection that follows it: W (alpha g + beta 1) + b = (alpha W) g + (b +
+    beta W 1).  Computed in float64 and rounded once -> (W' fp32, b' fp32)."""
+    w = proj_w.double()
+    return (w * float(alpha)).float().contiguous(), (proj_b.double() + float(beta) * w.sum(dim=1)).float().contiguous()
+
+
+def senet_g2_head_from_state_dict(sd):
+    """The SENet-G2+ head of a reference checkpoint (SENetG2Model's keys
+    g2_pool.{p,alpha,beta}, feature_proj.*, classifier.*, bare or under the
+    wrapper's leading ``backbone.``, a ``module.`` before either dropped;
+    trunk keys are ignored): p, alpha, beta as python floats, proj_w [F,2048],
+    proj_b, cls_w [classes,F], cls_b, and the folded proj_wf / proj_bf
+    (senet_g2_fold) as fp32 contiguous tensors."""
+    flat = _flat_keys(sd)
+    missing = [k for k in SENET_G2_HEAD_KEYS if k not in flat]
+    if missing:
+        raise ValueError(f"SENet-G2+ head: missing keys {missing}")
+    for k in SENET_G2_HEAD_KEYS[:3]:
+        if flat[k].numel() != 1:
+            raise ValueError(f"{k}: expected one element, got {tuple(flat[k].shape)}")
+    p, alpha, beta = (float(flat[k].reshape(-1)[0]) for k in SENET_G2_HEAD_KEYS[:3])
+    pw, cw = flat["feature_proj.weight"], flat["classifier.weight"]
+    if pw.dim() != 2 or flat["feature_proj.bias"].numel() != pw.shape[0]:
+        raise ValueError(f"feature_proj.weight: expected [F,C] with a bias [F], got {tuple(pw.shape)}")
+    if cw.dim() != 2 or cw.shape[1] != pw.shape[0] or flat["classifier.bias"].numel() != cw.shape[0]:
+        raise ValueError(f"classifier.weight: expected [classes,{pw.shape[0]}], got {tuple(cw.shape)}")
+    wf, bf = senet_g2_fold(pw, flat["feature_proj.bias"], alpha, beta)
+    return {"p": p, "alpha": alpha, "beta": beta, "proj_w": _f(pw), "proj_b": _f(flat["feature_proj.bias"]),
+            "proj_wf": wf, "proj_bf": bf, "cls_w": _f(cw), "cls_b": _f(flat["classifier.bias"])}
+
+
+def synthetic_senet_g2_head(seed, num_classes=8, feature_dim=2048, p=3.0, alpha=1.0, beta=0.0):
+    """Seeded SENet-G2+ head weights under SENetG2Model's keys: the two Linears
+    as PyTorch's default init, g2_pool's p / alpha / beta as given (the
+    reference starts them at gem_p / 1 / 0)."""
+    rs = np.random.RandomState(seed)
+    sd = collections.OrderedDict()
+    for k, v in (("p", p), ("alpha", alpha), ("beta", beta)):
+        sd[f"g2_pool.{k}"] = torch.tensor([v], dtype=torch.float32)
+    _lin(rs, sd, "feature_proj", feature_dim, 2048)
+    _lin(rs, sd, "classifier", num_classes, feature_dim)
+    return sd
+
+
 def resnet_conv_flops(arch, h, w, stride_on="3x3"):
     """Algorithmic FLOPs (2*M*N*K) of every trunk conv for one h x w image,
     following networks.ResNet.forward's strides/pads."""
