@@ -2,7 +2,7 @@
 // ResNet trunk plan").  No kernel lives here: a forward issues the library's
 // own entry points (rr_preprocess_u8_ex, rr_amax_f32, rr_stem_pool_h2,
 // rr_conv2d_h2, rr_bottleneck_out_h2, rr_maxpool2d) in the order
-// networks.ResNet._forward_h2 issues them, for the whole batch on the
+// networks.ResNet.maps issues them, for the whole batch on the
 // caller's stream or for two halves on the plan's two streams, one conv apart.
 #include <algorithm>
 #include <mutex>
@@ -27,6 +27,43 @@ namespace {
 
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline int conv_out(int n, int k, int s, int p) { return (n + 2 * p - k) / s + 1; }
+
+// One bottleneck of the walk below.
+struct Block {
+  int k, stage;                      // its number in forward order, its stage
+  bool entry, fused;                 // a stage's first block; its conv3 + downsample as one GEMM
+  bool stage_end, last;              // a stage's last block; the trunk's
+  int stride, s1, s2;                // the block's, conv1's and conv2's, as the stage layout has them
+  const rr_trunk_conv_t* down;       // the downsample conv where it is a launch of its own, else NULL
+  const rr_trunk_conv_t* c;          // c[0] conv1, c[1] conv2, c[2] conv3 or the fused [W3 | Wd]
+  int cin;                           // the block input's channels
+  int h, w, h1, w1, ho, wo;          // the maps: block input, after conv1, block output
+};
+
+// The one walk over a description's stages and blocks and its conv list (the
+// stem first, then per block [downsample,] conv1, conv2, conv3): f(Block) per
+// block, the maps following from h x w at the first block's input.  The list
+// must hold the layout's count of convs, each with a stride >= 1.
+template <class F>
+void walk_blocks(const rr_trunk_desc_t& d, const rr_trunk_conv_t* convs, int h, int w, F&& f) {
+  const rr_trunk_conv_t* c = convs + 1;
+  Block b{};
+  b.cin = convs->cout, b.h = h, b.w = w;
+  for (b.stage = 0; b.stage < d.n_stages; ++b.stage)
+    for (int bi = 0; bi < d.blocks[b.stage]; ++bi, ++b.k) {
+      b.entry = bi == 0, b.fused = b.entry && d.fuse_entry[b.stage];
+      b.stage_end = bi + 1 == d.blocks[b.stage], b.last = b.stage_end && b.stage + 1 == d.n_stages;
+      b.stride = (b.entry && b.stage > 0) ? 2 : 1;
+      b.s1 = d.stride_on ? b.stride : 1, b.s2 = d.stride_on ? 1 : b.stride;
+      b.down = (b.entry && !b.fused) ? c++ : nullptr;
+      b.c = c;
+      b.h1 = conv_out(b.h, c[0].kh, c[0].stride, c[0].pad), b.w1 = conv_out(b.w, c[0].kw, c[0].stride, c[0].pad);
+      b.ho = conv_out(b.h1, c[1].kh, c[1].stride, c[1].pad), b.wo = conv_out(b.w1, c[1].kw, c[1].stride, c[1].pad);
+      f(b);
+      b.cin = c[2].cout, b.h = b.ho, b.w = b.wo;
+      c += 3;
+    }
+}
 
 // One launch of a part's sequence.
 struct Op {
@@ -62,25 +99,14 @@ Shape trunk_shape(const rr_trunk_plan_s* p, int hgt, int wid) {
   h = (h - 1) / 2 + 1;
   w = (w - 1) / 2 + 1;
   s.max_x = std::max(s.max_x, (size_t)h * w * c->cout);
-  ++c;
-  for (int li = 0; li < p->d.n_stages; ++li) {
-    for (int bi = 0; bi < p->d.blocks[li]; ++bi) {
-      if (bi == 0 && !p->d.fuse_entry[li]) {
-        s.max_idn = std::max(s.max_idn, (size_t)conv_out(h, 1, c->stride, 0) * conv_out(w, 1, c->stride, 0) * c->cout);
-        ++c;
-      }
-      h = conv_out(h, c->kh, c->stride, c->pad), w = conv_out(w, c->kw, c->stride, c->pad);
-      s.max_y = std::max(s.max_y, (size_t)h * w * c->cout);
-      ++c;
-      h = conv_out(h, c->kh, c->stride, c->pad), w = conv_out(w, c->kw, c->stride, c->pad);
-      s.max_y = std::max(s.max_y, (size_t)h * w * c->cout);
-      ++c;
-      s.max_x = std::max(s.max_x, (size_t)h * w * c->cout);
-      ++c;
-    }
-    if (li == 2) s.h3 = h, s.w3 = w, s.c3 = (c - 1)->cout;
-  }
-  s.oh = h, s.ow = w;
+  walk_blocks(p->d, c, h, w, [&](const Block& b) {
+    // (a validated downsample conv has the block's stride: its map is the block's output map)
+    if (b.down) s.max_idn = std::max(s.max_idn, (size_t)b.ho * b.wo * b.down->cout);
+    s.max_y = std::max(s.max_y, std::max((size_t)b.h1 * b.w1 * b.c[0].cout, (size_t)b.ho * b.wo * b.c[1].cout));
+    s.max_x = std::max(s.max_x, (size_t)b.ho * b.wo * b.c[2].cout);
+    if (b.stage == 2 && b.stage_end) s.h3 = b.ho, s.w3 = b.wo, s.c3 = b.c[2].cout;
+    s.oh = b.ho, s.ow = b.wo;
+  });
   return s;
 }
 
@@ -154,62 +180,49 @@ void build_ops(const rr_trunk_plan_s* p, const Shape& s, const uint8_t* img, int
   }
   h = (h - 1) / 2 + 1;
   w = (w - 1) / 2 + 1;
-  ++c;
   const float* cur = X[0];
   int cur_i = 0;  // which workspace block buffer holds cur (-1: an output tensor)
   const unsigned* xa = R(1);
-  int r = 2, ci = 1;
-  for (int li = 0; li < p->d.n_stages; ++li) {
-    for (int bi = 0; bi < p->d.blocks[li]; ++bi) {
-      const bool entry = bi == 0, fused = entry && p->d.fuse_entry[li];
-      const bool last_of_stage = bi + 1 == p->d.blocks[li];
-      const int hx = h, wx = w;
-      const float* idn = cur;
-      if (entry && !fused) {
-        o = Op{};
-        o.kind = Op::CONV, o.c = c, o.x = cur, o.xa = xa, o.y = IDN, o.b = b, o.h = h, o.w = w;
-        ops.push_back(o);
-        idn = IDN;
-        ++c;
-      }
+  walk_blocks(p->d, c, h, w, [&](const Block& k) {
+    const int r = 2 + 3 * k.k, ci = 1 + 3 * k.k;
+    const float* idn = cur;
+    if (k.down) {
       o = Op{};
-      o.kind = Op::CONV, o.c = c, o.x = cur, o.xa = xa, o.y = Y[0], o.ya = R(r), o.b = b, o.h = h, o.w = w, o.hook = ci;
+      o.kind = Op::CONV, o.c = k.down, o.x = cur, o.xa = xa, o.y = IDN, o.b = b, o.h = k.h, o.w = k.w;
       ops.push_back(o);
-      h = conv_out(h, c->kh, c->stride, c->pad), w = conv_out(w, c->kw, c->stride, c->pad);
-      ++c;
-      o = Op{};
-      o.kind = Op::CONV, o.c = c, o.x = Y[0], o.xa = R(r), o.y = Y[1], o.ya = R(r + 1), o.b = b, o.h = h, o.w = w,
-      o.hook = ci + 1;
-      ops.push_back(o);
-      h = conv_out(h, c->kh, c->stride, c->pad), w = conv_out(w, c->kw, c->stride, c->pad);
-      ++c;
-      // where the block's output goes: an output tensor, or the free block buffer
-      float* dst;
-      unsigned* dsta = R(r + 2);
-      int dst_i = -1;
-      if (last_of_stage && li + 1 == p->d.n_stages) {
-        dst = x4, dsta = rec_x4;
-      } else if (last_of_stage && li == 2 && x3) {
-        dst = x3;
-        if (rec_x3) dsta = rec_x3;
-        else *own_x3_rec = dsta;
-      } else {
-        dst_i = cur_i == 0 ? 1 : 0;
-        dst = X[dst_i];
-      }
-      o = Op{};
-      o.c = c, o.x = Y[1], o.xa = R(r + 1), o.y = dst, o.ya = dsta, o.b = b, o.h = h, o.w = w, o.hook = ci + 2;
-      if (fused) {
-        o.kind = Op::ENTRY, o.x2 = cur, o.x2a = xa, o.h2 = hx, o.w2 = wx;
-      } else {
-        o.kind = Op::CONV, o.x2 = idn;
-      }
-      ops.push_back(o);
-      ++c;
-      cur = dst, cur_i = dst_i, xa = dsta;
-      r += 3, ci += 3;
+      idn = IDN;
     }
-  }
+    o = Op{};
+    o.kind = Op::CONV, o.c = k.c, o.x = cur, o.xa = xa, o.y = Y[0], o.ya = R(r), o.b = b, o.h = k.h, o.w = k.w, o.hook = ci;
+    ops.push_back(o);
+    o = Op{};
+    o.kind = Op::CONV, o.c = k.c + 1, o.x = Y[0], o.xa = R(r), o.y = Y[1], o.ya = R(r + 1), o.b = b, o.h = k.h1, o.w = k.w1,
+    o.hook = ci + 1;
+    ops.push_back(o);
+    // where the block's output goes: an output tensor, or the free block buffer
+    float* dst;
+    unsigned* dsta = R(r + 2);
+    int dst_i = -1;
+    if (k.last) {
+      dst = x4, dsta = rec_x4;
+    } else if (k.stage_end && k.stage == 2 && x3) {
+      dst = x3;
+      if (rec_x3) dsta = rec_x3;
+      else *own_x3_rec = dsta;
+    } else {
+      dst_i = cur_i == 0 ? 1 : 0;
+      dst = X[dst_i];
+    }
+    o = Op{};
+    o.c = k.c + 2, o.x = Y[1], o.xa = R(r + 1), o.y = dst, o.ya = dsta, o.b = b, o.h = k.ho, o.w = k.wo, o.hook = ci + 2;
+    if (k.fused) {
+      o.kind = Op::ENTRY, o.x2 = cur, o.x2a = xa, o.h2 = k.h, o.w2 = k.w;
+    } else {
+      o.kind = Op::CONV, o.x2 = idn;
+    }
+    ops.push_back(o);
+    cur = dst, cur_i = dst_i, xa = dsta;
+  });
 }
 
 int issue(rr_handle_s* h, const rr_trunk_plan_s* p, const Op& o, hipStream_t s) {
@@ -270,29 +283,22 @@ int rr_trunk_h2_create(rr_handle_t h, const rr_trunk_desc_t* d, rr_trunk_plan_t*
   if (c->cin != 4 || (d->fuse_stem_pool && c->cout != 64) || !c->relu)
     return set_error(h, RR_EINVAL, "rr_trunk_h2_create: the stem reads NHWC4, has a ReLU and, fused with its pool, cout 64");
   int ch = c->cout;
-  ++c;
-  for (int li = 0; li < d->n_stages; ++li)
-    for (int bi = 0; bi < d->blocks[li]; ++bi) {
-      const int stride = (bi == 0 && li > 0) ? 2 : 1;
-      const int s1 = d->stride_on ? stride : 1, s2 = d->stride_on ? 1 : stride;
-      const bool entry = bi == 0, fused = entry && d->fuse_entry[li];
-      bool ok = true;
-      if (entry && !fused) {
-        ok = ok && c->cin == ch && c->kh == 1 && c->kw == 1 && c->stride == stride && c->pad == 0 && !c->relu &&
-             !c->residual && c->cout == c[3].cout;
-        ++c;
-      }
-      ok = ok && c[0].cin == ch && c[0].kh == 1 && c[0].kw == 1 && c[0].stride == s1 && c[0].pad == 0 && c[0].relu;
-      ok = ok && c[1].cin == c[0].cout && c[1].kh == 3 && c[1].kw == 3 && c[1].stride == s2 && c[1].pad == 1 && c[1].relu;
-      ok = ok && c[2].kh == 1 && c[2].kw == 1 && c[2].pad == 0 && c[2].relu;
-      if (fused)
-        ok = ok && c[2].cin == c[1].cout + ch && c[2].stride == stride && !c[2].residual && c[2].cout % 256 == 0;
-      else
-        ok = ok && c[2].cin == c[1].cout && c[2].stride == 1 && c[2].residual && (entry || c[2].cout == ch);
-      if (!ok) return set_error(h, RR_EINVAL, "rr_trunk_h2_create: a block's convs do not fit the layout");
-      ch = c[2].cout;
-      c += 3;
-    }
+  bool ok = true;
+  walk_blocks(*d, c, 0, 0, [&](const Block& b) {
+    const rr_trunk_conv_t* c = b.c;
+    if (b.down)
+      ok = ok && b.down->cin == b.cin && b.down->kh == 1 && b.down->kw == 1 && b.down->stride == b.stride &&
+           b.down->pad == 0 && !b.down->relu && !b.down->residual && b.down->cout == c[2].cout;
+    ok = ok && c[0].cin == b.cin && c[0].kh == 1 && c[0].kw == 1 && c[0].stride == b.s1 && c[0].pad == 0 && c[0].relu;
+    ok = ok && c[1].cin == c[0].cout && c[1].kh == 3 && c[1].kw == 3 && c[1].stride == b.s2 && c[1].pad == 1 && c[1].relu;
+    ok = ok && c[2].kh == 1 && c[2].kw == 1 && c[2].pad == 0 && c[2].relu;
+    if (b.fused)
+      ok = ok && c[2].cin == c[1].cout + b.cin && c[2].stride == b.stride && !c[2].residual && c[2].cout % 256 == 0;
+    else
+      ok = ok && c[2].cin == c[1].cout && c[2].stride == 1 && c[2].residual && (b.entry || c[2].cout == b.cin);
+    ch = c[2].cout;
+  });
+  if (!ok) return set_error(h, RR_EINVAL, "rr_trunk_h2_create: a block's convs do not fit the layout");
   rr_trunk_plan_s* p = new (std::nothrow) rr_trunk_plan_s();
   if (!p) return set_error(h, RR_EINVAL, "rr_trunk_h2_create: out of memory");
   p->d = *d;

@@ -21,164 +21,98 @@ def _check_conv_math(conv_math):
         raise ValueError("conv_math must be 'h2' or 'f32'")
 
 
-def _load_trunk_convs(net, sd, arch, device, conv_math):
-    """What the bottleneck trunks' constructors share: the torchvision-keyed
-    convs of sd (arch: a weights.RESNET_LAYERS name) with their BNs folded, on
-    the device in net.convs, the stem padded to 4 input channels; on the f16x2
-    core the split weights in net.convs_h2."""
-    net.device = torch.device(device)
-    folded = W.folded_resnet(sd, arch)
-    # stem weights padded to 4 input channels (zero) for the NHWC4 tap path
-    w1, b1 = folded["conv1"]
-    folded["conv1"] = (torch.nn.functional.pad(w1, (0, 1)).contiguous(), b1)
-    net.convs = {k: (w.to(net.device), b.to(net.device)) for k, (w, b) in folded.items()}
-    net.layers = W.RESNET_LAYERS[arch]
-    net.conv_math = conv_math
-    net.convs_h2 = {}
-    if conv_math == "h2":
-        net.convs_h2 = {k: ops.H2Conv(w) for k, (w, _) in net.convs.items()}
-        # the stem conv + ReLU + max-pool as one launch (ops.stem_pool_h2)
-        net.fuse_stem_pool = True
-
-
-def _stem_h2(net, x, rec):
-    """The f16x2 stem of a bottleneck trunk: x's record into rec[0], then the
-    stem conv, its ReLU and the max-pool (one launch where net.fuse_stem_pool
-    and the stem has 64 channels), the output's record in rec[1]."""
-    cv, h2 = net.convs, net.convs_h2
-    ops.amax_f32(x, rec[0])
-    if net.fuse_stem_pool and h2["conv1"].cout == 64:
-        return ops.stem_pool_h2(x, rec[0], h2["conv1"], cv["conv1"][1], 2, 3, rec[1])
-    x = ops.conv2d_h2(x, rec[0], h2["conv1"], cv["conv1"][1], 2, 3, None, True, rec[1])
-    return ops.maxpool2d(x, 3, 2, 1)
-
-
-class ResNet:
-    """torchvision resnet children[:-2] trunk (networks/backbone.py:60-109:
-    block1 = conv1/bn1/relu/maxpool, block2..5 = layer1..4), NHWC, BN folded.
-
-    forward(x_nhwc [B,H,W,3]) -> [B,H/32,W/32,2048] NHWC.
-
-    conv_math: "h2" (default) runs every conv, the stem included (NHWC4
-    taps, K padded to 224), on the f16x2 split core (fp32-accurate: per conv
-    mean error vs float64 within 1.05x and max within 1.25x of the exact-fp32
-    core's, descriptors within 2x and <= 1e-6, tests/test_gpu_h2.py; three
-    fp16 MFMAs per product; weights split once here, each conv publishes max
-    |y| for the next one's split scale); "f32" keeps all convs on the
-    exact-fp32 MFMA core.  (The split-bf16 core, "s3", was retired in round 6.)
-
-    stride_on: "3x3" (default) = torchvision v1.5 bottlenecks; "1x1" = the
-    reference's own torchvision-free R101, ResNet_DOLG
-    (networks/backbone.py:218-274, BottleneckTransform :305-325: the stride of
-    a stage's first block sits on the 1x1 `a` conv).  A ResNet_DOLG state dict
-    (stem.*, s{K}.b{M}.*) is accepted as is (weights.to_torchvision_keys)."""
+class _BottleneckTrunk:
+    """What the bottleneck trunks (ResNet, SENet) share: the folded convs, the
+    stem, forward() and maps(), the one walk over the block schedule
+    (self.blocks = weights.trunk_blocks).  A subclass supplies _block(x, xa, b,
+    rec, hook, ci): block b on x (record xa) -> its output, rec the block's
+    three zeroed records (conv1's output, conv2's, the block's) on the f16x2
+    core and None on "f32", hook(ci), hook(ci + 1), hook(ci + 2) called after
+    its three convs."""
 
     outputdim_block5 = 2048
     outputdim_block4 = 1024
 
-    def __init__(self, name="resnet101", state_dict=None, seed=0, device="cuda", conv_math="h2", stride_on="3x3"):
-        _check_conv_math(conv_math)
-        W.block_strides(1, stride_on)  # validates
+    def _load_trunk_convs(self, sd, arch, device, conv_math, stride_on="3x3"):
+        """The torchvision-keyed convs of sd (arch: a weights.RESNET_LAYERS
+        name) with their BNs folded, on the device in self.convs, the stem
+        padded to 4 input channels; on the f16x2 core the split weights in
+        self.convs_h2."""
+        self.device = torch.device(device)
         self.stride_on = stride_on
-        if name not in W.RESNET_LAYERS:
-            raise ValueError(f"Unsupported or unknown architecture: {name}!")
-        self.name = name
-        sd = W.synthetic_resnet_state_dict(name, seed) if state_dict is None else W.to_torchvision_keys(state_dict)
-        _load_trunk_convs(self, sd, name, device, conv_math)
+        self.blocks = W.trunk_blocks(arch, stride_on)
+        folded = W.folded_resnet(sd, arch)
+        # stem weights padded to 4 input channels (zero) for the NHWC4 tap path
+        w1, b1 = folded["conv1"]
+        folded["conv1"] = (torch.nn.functional.pad(w1, (0, 1)).contiguous(), b1)
+        self.convs = {k: (w.to(self.device), b.to(self.device)) for k, (w, b) in folded.items()}
+        self.layers = W.RESNET_LAYERS[arch]
+        self.conv_math = conv_math
+        self.convs_h2 = {}
         if conv_math == "h2":
-            # each stage's first block: conv3 + downsample as one GEMM (ops.H2Bottleneck)
-            self.fuse_downsample = True
-            self.bneck_h2 = {}
-            for li in range(len(self.layers)):
-                p = f"layer{li + 1}.0"
-                (w3, b3), (wd, bd) = self.convs[p + ".conv3"], self.convs[p + ".downsample.0"]
-                if w3.shape[0] % 256 == 0:
-                    self.bneck_h2[p] = ops.H2Bottleneck(w3, b3, wd, bd)
+            self.convs_h2 = {k: ops.H2Conv(w) for k, (w, _) in self.convs.items()}
+            # the stem conv + ReLU + max-pool as one launch (ops.stem_pool_h2)
+            self.fuse_stem_pool = True
 
-    def _conv(self, x, name, stride, pad, relu, residual=None):
+    def _stem_h2(self, x, rec):
+        """The f16x2 stem: x's record into rec[0], then the stem conv, its ReLU
+        and the max-pool (one launch where self.fuse_stem_pool and the stem has
+        64 channels, so the stem's full-resolution map never reaches HBM), the
+        output's record in rec[1]: the max-pool output reuses the stem's (every
+        stem output lies in some 3x3/2 window, so the max is the same)."""
+        cv, h2 = self.convs, self.convs_h2
+        ops.amax_f32(x, rec[0])
+        if self.fuse_stem_pool and h2["conv1"].cout == 64:
+            return ops.stem_pool_h2(x, rec[0], h2["conv1"], cv["conv1"][1], 2, 3, rec[1])
+        x = ops.conv2d_h2(x, rec[0], h2["conv1"], cv["conv1"][1], 2, 3, None, True, rec[1])
+        return ops.maxpool2d(x, 3, 2, 1)
+
+    def _conv(self, x, xa, name, stride, pad, relu, residual=None, ya=None):
+        """One folded conv on the trunk's core (xa / ya: the input's and the
+        output's max-|x| record, read by the f16x2 core alone)."""
         w, b = self.convs[name]
+        if self.conv_math == "h2":
+            return ops.conv2d_h2(x, xa, self.convs_h2[name], b, stride, pad, residual, relu, ya)
         return ops.conv2d(x, w, b, stride, pad, residual, relu)
 
-    def plan(self, lag=1):
-        """The f16x2 trunk as a native plan (ops.TrunkPlan, built on first use,
-        one per lag): uint8 pixels -> x4 (x3) and their records in one call, the
-        same launches as _forward_h2 under the current fuse_downsample /
-        fuse_stem_pool."""
-        plans = self.__dict__.setdefault("_plans", {})
-        key = (lag, bool(self.fuse_downsample), bool(self.fuse_stem_pool))
-        if key not in plans:
-            plans[key] = ops.TrunkPlan(self, lag)
-        return plans[key]
-
-    def _forward_h2(self, x, hook, want_x3):
-        """maps() on the f16x2 core: every conv reads its input's max-|x|
-        record and writes its output's (one zeroed [2 + 3 blocks, 64] tensor per
-        forward); the max-pool output reuses the stem's record (every stem
-        output lies in some 3x3/2 window, so the max is the same); the stem,
-        its ReLU and the max-pool run as one launch (ops.stem_pool_h2), so the
-        stem's full-resolution map never reaches HBM.  A stage's
-        first block runs conv3 and its downsample projection as one GEMM
-        (ops.bottleneck_out_h2), so the projected identity never reaches HBM.
-        hook(i), if given, is called after the i-th conv launch (i = 0: the
-        stem) -- the point where a caller can record a stream event.  The
-        records returned are the ones x3's and x4's conv3 published, for a
-        caller that runs another f16x2 conv on either map."""
-        cv, h2 = self.convs, self.convs_h2
-        hook = hook or (lambda i: None)
-        rec = ops.amax_records(2 + 3 * sum(self.layers), x.device)
-        x = _stem_h2(self, x, rec)
-        hook(0)
-        xa, r, x3, x3a, ci = rec[1], 2, None, None, 1
-        for li, nb in enumerate(self.layers):
-            for bi in range(nb):
-                p = f"layer{li + 1}.{bi}"
-                s1, s2 = W.block_strides(2 if (bi == 0 and li > 0) else 1, self.stride_on)
-                d = f"{p}.downsample.0"
-                fused = bi == 0 and self.fuse_downsample and p in self.bneck_h2
-                idn = ops.conv2d_h2(x, xa, h2[d], cv[d][1], s1 * s2, 0, None, False) if bi == 0 and not fused else x
-                y = ops.conv2d_h2(x, xa, h2[f"{p}.conv1"], cv[f"{p}.conv1"][1], s1, 0, None, True, rec[r])
-                hook(ci)
-                y = ops.conv2d_h2(y, rec[r], h2[f"{p}.conv2"], cv[f"{p}.conv2"][1], s2, 1, None, True, rec[r + 1])
-                hook(ci + 1)
-                if fused:
-                    x = ops.bottleneck_out_h2(y, rec[r + 1], x, xa, self.bneck_h2[p], s1 * s2, rec[r + 2])
-                else:
-                    x = ops.conv2d_h2(y, rec[r + 1], h2[f"{p}.conv3"], cv[f"{p}.conv3"][1], 1, 0, idn, True,
-                                      rec[r + 2])
-                hook(ci + 2)
-                ci += 3
-                xa, r = rec[r + 2], r + 3
-            if li == 2:
-                x3, x3a = x, xa
-        return (x3, x, x3a, xa) if want_x3 else (None, x, None, xa)
-
-    def maps(self, x, hook=None, want_x3=False):
+    def maps(self, x, hook=None, want_x3=False, **block_kw):
         """x: NHWC fp32 with 3 channels or 4 (zero 4th channel, preferred) ->
         (x3, x4, x3_amax, x4_amax), the order _Extractor._tail and
         ops.TrunkPlan.forward_u8(return_x3=True) use: layer3's and layer4's
         outputs (ResNet_DOLG.forward's (x3, x4), networks/backbone.py:236-242)
-        and their max-|x| records.  The records are None on the "f32" trunk;
-        x3 and its record are None unless want_x3, so a caller that never reads
-        x3 does not keep it alive.  hook: see _forward_h2 (the "f32" trunk
-        never calls it)."""
+        and their max-|x| records, the ones x3's and x4's last launch
+        published, for a caller that runs another f16x2 conv on either map.
+        The records are None on the "f32" trunk; x3 and its record are None
+        unless want_x3, so a caller that never reads x3 does not keep it alive.
+
+        On the f16x2 core every conv reads its input's max-|x| record and
+        writes its output's (one zeroed [2 + 3 blocks, 64] tensor per forward,
+        block k's three at [2 + 3 k, 5 + 3 k)), and hook(i), if given, is
+        called after the i-th conv launch (i = 0: the stem and its pool; a
+        downsample projection launched by itself is not counted) -- the point
+        where a caller can record a stream event.  The "f32" trunk never calls
+        it.  block_kw: passed on to the subclass's _block."""
         if x.shape[-1] == 3:
             x = torch.nn.functional.pad(x, (0, 1))
-        if self.conv_math == "h2":
-            return self._forward_h2(x.contiguous(), hook, want_x3)
-        x = self._conv(x, "conv1", 2, 3, True)
-        x = ops.maxpool2d(x, 3, 2, 1)
-        x3 = None
-        for li, nb in enumerate(self.layers):
-            for bi in range(nb):
-                p = f"layer{li + 1}.{bi}"
-                s1, s2 = W.block_strides(2 if (bi == 0 and li > 0) else 1, self.stride_on)
-                idn = self._conv(x, f"{p}.downsample.0", s1 * s2, 0, False) if bi == 0 else x
-                y = self._conv(x, f"{p}.conv1", s1, 0, True)
-                y = self._conv(y, f"{p}.conv2", s2, 1, True)
-                x = self._conv(y, f"{p}.conv3", 1, 0, True, residual=idn)
-            if li == 2:
-                x3 = x
-        return (x3 if want_x3 else None), x, None, None
+        x = x.contiguous()
+        h2 = self.conv_math == "h2"
+        hook = (hook if h2 else None) or _no_hook
+        rec = xa = x3 = x3a = None
+        if h2:
+            rec = ops.amax_records(2 + 3 * len(self.blocks), x.device)
+            x = self._stem_h2(x, rec)
+            hook(0)
+            xa = rec[1]
+        else:
+            x = ops.maxpool2d(self._conv(x, None, "conv1", 2, 3, True), 3, 2, 1)
+        for k, b in enumerate(self.blocks):
+            r = rec[2 + 3 * k:5 + 3 * k] if h2 else None
+            x = self._block(x, xa, b, r, hook, 1 + 3 * k, **block_kw)
+            if h2:
+                xa = r[2]
+            if b.stage == 2 and b.stage_end:
+                x3, x3a = x, xa
+        return (x3, x, x3a, xa) if want_x3 else (None, x, None, xa)
 
     def forward(self, x, return_x3=False, hook=None, return_x3_amax=False, return_amax=False):
         """A selection from maps(x, hook, return_x3): x4; with return_x3 (x3,
@@ -199,29 +133,130 @@ class ResNet:
     __call__ = forward
 
 
-class SENet:
+def _no_hook(i):
+    pass
+
+
+class ResNet(_BottleneckTrunk):
+    """torchvision resnet children[:-2] trunk (networks/backbone.py:60-109:
+    block1 = conv1/bn1/relu/maxpool, block2..5 = layer1..4), NHWC, BN folded.
+
+    forward(x_nhwc [B,H,W,3]) -> [B,H/32,W/32,2048] NHWC.
+
+    conv_math: "h2" (default) runs every conv, the stem included (NHWC4
+    taps, K padded to 224), on the f16x2 split core (fp32-accurate: per conv
+    mean error vs float64 within 1.05x and max within 1.25x of the exact-fp32
+    core's, descriptors within 2x and <= 1e-6, tests/test_gpu_h2.py; three
+    fp16 MFMAs per product; weights split once here, each conv publishes max
+    |y| for the next one's split scale); "f32" keeps all convs on the
+    exact-fp32 MFMA core.  (The split-bf16 core, "s3", was retired in round 6.)
+    On "h2" a stage's first block runs conv3 and its downsample projection as
+    one GEMM (ops.bottleneck_out_h2, where fuse_downsample is set and conv3's
+    Cout is a multiple of 256), so the projected identity never reaches HBM.
+
+    stride_on: "3x3" (default) = torchvision v1.5 bottlenecks; "1x1" = the
+    reference's own torchvision-free R101, ResNet_DOLG
+    (networks/backbone.py:218-274, BottleneckTransform :305-325: the stride of
+    a stage's first block sits on the 1x1 `a` conv).  A ResNet_DOLG state dict
+    (stem.*, s{K}.b{M}.*) is accepted as is (weights.to_torchvision_keys)."""
+
+    def __init__(self, name="resnet101", state_dict=None, seed=0, device="cuda", conv_math="h2", stride_on="3x3"):
+        _check_conv_math(conv_math)
+        W.block_strides(1, stride_on)  # validates
+        if name not in W.RESNET_LAYERS:
+            raise ValueError(f"Unsupported or unknown architecture: {name}!")
+        self.name = name
+        sd = W.synthetic_resnet_state_dict(name, seed) if state_dict is None else W.to_torchvision_keys(state_dict)
+        self._load_trunk_convs(sd, name, device, conv_math, stride_on)
+        if conv_math == "h2":
+            # each stage's first block: conv3 + downsample as one GEMM (ops.H2Bottleneck)
+            self.fuse_downsample = True
+            self.bneck_h2 = {}
+            for b in self.blocks:
+                if b.entry and b.cout % 256 == 0:
+                    (w3, b3), (wd, bd) = self.convs[b.prefix + ".conv3"], self.convs[b.prefix + ".downsample.0"]
+                    self.bneck_h2[b.prefix] = ops.H2Bottleneck(w3, b3, wd, bd)
+
+    def _fused_entry(self, b):
+        """Block b runs conv3 + its downsample projection as one GEMM (read per call: tests flip the flag)."""
+        return b.entry and self.conv_math == "h2" and bool(self.fuse_downsample) and b.prefix in self.bneck_h2
+
+    def _block(self, x, xa, b, rec, hook, ci):
+        p, fused = b.prefix, self._fused_entry(b)
+        r0, r1, r2 = rec if rec is not None else (None, None, None)
+        idn = self._conv(x, xa, p + ".downsample.0", b.stride, 0, False) if b.entry and not fused else x
+        y = self._conv(x, xa, p + ".conv1", b.s1, 0, True, None, r0)
+        hook(ci)
+        y = self._conv(y, r0, p + ".conv2", b.s2, 1, True, None, r1)
+        hook(ci + 1)
+        if fused:
+            x = ops.bottleneck_out_h2(y, r1, x, xa, self.bneck_h2[p], b.stride, r2)
+        else:
+            x = self._conv(y, r1, p + ".conv3", 1, 0, True, idn, r2)
+        hook(ci + 2)
+        return x
+
+    def plan_convs(self):
+        """The f16x2 trunk's convs in the order the native plan (ops.TrunkPlan,
+        rr_trunk_h2_create) takes them, under the current fuse_downsample:
+        (convs, fuse_entry), fuse_entry per stage, convs the stem, then per
+        block the downsample projection where it is a launch of its own,
+        conv1, conv2, and conv3 or the fused [W3 | Wd].  A conv is
+        rr_trunk_conv_t's fields with tensors for pointers: (planes, iscale,
+        bias, cin, cout, kh, kw, stride, pad, residual, relu)."""
+        def conv(name, stride, pad, residual, relu):
+            c = self.convs_h2[name]
+            return (c.planes, c.iscale, self.convs[name][1], c.cin, c.cout, c.kh, c.kw, stride, pad, residual, relu)
+
+        convs, fuse_entry = [conv("conv1", 2, 3, False, True)], []
+        for b in self.blocks:
+            p, fused = b.prefix, self._fused_entry(b)
+            if b.entry:
+                fuse_entry.append(fused)
+                if not fused:
+                    convs.append(conv(p + ".downsample.0", b.stride, 0, False, False))
+            convs.append(conv(p + ".conv1", b.s1, 0, False, True))
+            convs.append(conv(p + ".conv2", b.s2, 1, False, True))
+            if fused:
+                e = self.bneck_h2[p]
+                convs.append((e.planes2, e.iscale, e.bias, e.planes + e.cin, e.cout, 1, 1, b.stride, 0, False, True))
+            else:
+                convs.append(conv(p + ".conv3", 1, 0, True, True))
+        return convs, fuse_entry
+
+    def plan(self, lag=1):
+        """The f16x2 trunk as a native plan (ops.TrunkPlan, built on first use,
+        one per lag): uint8 pixels -> x4 (x3) and their records in one call, the
+        same launches as maps() under the current fuse_downsample /
+        fuse_stem_pool."""
+        plans = self.__dict__.setdefault("_plans", {})
+        key = (lag, bool(self.fuse_downsample), bool(self.fuse_stem_pool))
+        if key not in plans:
+            plans[key] = ops.TrunkPlan(self, lag)
+        return plans[key]
+
+
+class SENet(_BottleneckTrunk):
     """The SE-ResNet trunk of models/senet_g2.py:32-129 (SEBottleneck, SENet),
     NHWC, BN folded: torchvision-v1.5 bottlenecks (the stride on the 3x3, :41)
     whose conv3 + bn3 output is gated per channel by a Squeeze-and-Excitation
     block (:12-29) before the identity is added.  name: "senet50" = (3, 4, 6,
     3) or "senet101" = (3, 4, 23, 3); reduction: the SE blocks' (default 16).
 
-    maps() has ResNet.maps' contract.  Launches per block: conv1, conv2, conv3
-    WITHOUT residual, ReLU or record (a stage's first block: its downsample
-    projection as a separate conv before them; no fused conv3 + downsample
-    GEMM, whose epilogue cannot gate one half of its sum), then
+    maps() is the trunks' shared walk, with taps: a dict that receives {block
+    prefix: {mean, hidden, gate}} (tests).  Launches per block: conv1, conv2,
+    conv3 WITHOUT residual, ReLU or record (a stage's first block: its
+    downsample projection as a separate conv before them; no fused conv3 +
+    downsample GEMM, whose epilogue cannot gate one half of its sum), then
     ops.se_squeeze, ops.linear_splitk (fc.0 + ReLU) and ops.se_apply in place
     on conv3's output (fc.2, the sigmoid, the scale, the identity, the ReLU),
     which on the f16x2 core publishes the block's max-|x| record for the next
-    block's convs.  There is no plan(): the native trunk plan knows no SE
-    block.
+    block's convs.  There is no plan(): the native trunk plan has no SE
+    launches.
 
     state_dict: conv / BN keys as ResNet accepts them, plus
     layerN.M.se.fc.{0,2}.weight (weights.senet_se_from_state_dict); None: the
     seeded weights.synthetic_senet_state_dict."""
-
-    outputdim_block5 = 2048
-    outputdim_block4 = 1024
 
     def __init__(self, name="senet50", state_dict=None, seed=0, device="cuda", conv_math="h2", reduction=16):
         _check_conv_math(conv_math)
@@ -231,16 +266,8 @@ class SENet:
         self.reduction = W.senet_check_reduction(reduction)
         sd = W.synthetic_senet_state_dict(name, seed, reduction) if state_dict is None else state_dict
         se = W.senet_se_from_state_dict(sd, name, reduction)
-        _load_trunk_convs(self, W.to_torchvision_keys(sd), W.SENET_TRUNKS[name], device, conv_math)
+        self._load_trunk_convs(W.to_torchvision_keys(sd), W.SENET_TRUNKS[name], device, conv_math)
         self.se = {p: (w1.to(self.device), w2.to(self.device)) for p, (w1, w2) in se.items()}
-
-    def _conv(self, x, xa, name, stride, pad, relu, ya=None):
-        """One folded conv on the trunk's core (xa / ya: the input's and the
-        output's max-|x| record, read by the f16x2 core alone)."""
-        w, b = self.convs[name]
-        if self.conv_math == "h2":
-            return ops.conv2d_h2(x, xa, self.convs_h2[name], b, stride, pad, None, relu, ya)
-        return ops.conv2d(x, w, b, stride, pad, None, relu)
 
     def block(self, x, xa, p, entry, stride, rec=None, hook=None, ci=0, taps=None):
         """SEBottleneck.forward (:51-72) for block p on x (record xa): entry =
@@ -249,11 +276,11 @@ class SENet:
         core, None on "f32".  taps: a dict that receives mean, hidden and gate
         (tests).  Returns the block's output; its record is rec[2]."""
         r0, r1, r2 = rec if rec is not None else (None, None, None)
-        hook = hook or (lambda i: None)
+        hook = hook or _no_hook
         idn = self._conv(x, xa, f"{p}.downsample.0", stride, 0, False) if entry else x
-        y = self._conv(x, xa, f"{p}.conv1", 1, 0, True, r0)
+        y = self._conv(x, xa, f"{p}.conv1", 1, 0, True, None, r0)
         hook(ci)
-        y = self._conv(y, r0, f"{p}.conv2", stride, 1, True, r1)
+        y = self._conv(y, r0, f"{p}.conv2", stride, 1, True, None, r1)
         hook(ci + 1)
         y = self._conv(y, r1, f"{p}.conv3", 1, 0, False)
         hook(ci + 2)
@@ -266,40 +293,9 @@ class SENet:
             return got[0]
         return got
 
-    def maps(self, x, hook=None, want_x3=False, taps=None):
-        """ResNet.maps' contract: NHWC fp32 pixels (3 or 4 channels) -> (x3, x4,
-        x3_amax, x4_amax), records None on the "f32" trunk.  taps: a dict that
-        receives {block prefix: {mean, hidden, gate}} (tests)."""
-        if x.shape[-1] == 3:
-            x = torch.nn.functional.pad(x, (0, 1))
-        x = x.contiguous()
-        h2 = self.conv_math == "h2"
-        hook = hook or (lambda i: None)
-        rec, xa = None, None
-        if h2:
-            rec = ops.amax_records(2 + 3 * sum(self.layers), x.device)
-            x = _stem_h2(self, x, rec)
-            hook(0)
-            xa = rec[1]
-        else:
-            w, b = self.convs["conv1"]
-            x = ops.maxpool2d(ops.conv2d(x, w, b, 2, 3, None, True), 3, 2, 1)
-        r, ci, x3, x3a = 2, 1, None, None
-        for li, nb in enumerate(self.layers):
-            for bi in range(nb):
-                p = f"layer{li + 1}.{bi}"
-                t = None if taps is None else taps.setdefault(p, {})
-                x = self.block(x, xa, p, bi == 0, 2 if (bi == 0 and li > 0) else 1, rec[r:r + 3] if h2 else None,
-                               hook if h2 else None, ci, t)
-                if h2:
-                    xa = rec[r + 2]
-                r, ci = r + 3, ci + 3
-            if li == 2:
-                x3, x3a = x, xa
-        return (x3, x, x3a, xa) if want_x3 else (None, x, None, xa)
-
-    forward = ResNet.forward
-    __call__ = forward
+    def _block(self, x, xa, b, rec, hook, ci, taps=None):
+        return self.block(x, xa, b.prefix, b.entry, b.stride, rec, hook, ci,
+                          None if taps is None else taps.setdefault(b.prefix, {}))
 
 
 class gem:
@@ -366,7 +362,7 @@ class _Extractor:
         raise NotImplementedError
 
     def forward_test_nhwc(self, x_nhwc, hook=None):
-        """hook: ResNet._forward_h2's (forward_test_u8_streams records its gate there)."""
+        """hook: the trunk's maps()'s (forward_test_u8_streams records its gate there)."""
         t = self._trunk()
         if t is None:
             raise NotImplementedError
@@ -381,7 +377,7 @@ class _Extractor:
         """uint8 [B,H,W,3] pixels -> descriptors, with ToTensor+Normalize fused
         into the first kernel (dataset/configdataset.py:417).  A ResNet-based
         extractor on the f16x2 core runs its trunk as one native call
-        (ops.TrunkPlan: the launches of ResNet._forward_h2, in two parts on two
+        (ops.TrunkPlan: the launches of ResNet.maps, in two parts on two
         streams where the batch is large enough) and its tail on the current
         stream after the plan's join."""
         x = img_nhwc_u8
@@ -397,7 +393,7 @@ class _Extractor:
     def forward_test_u8_streams(self, img_nhwc_u8, streams, lag=1):
         """forward_test_u8 with the batch cut into len(streams) contiguous parts,
         part i on HIP stream streams[i], part i + 1 held back until part i has
-        launched its lag-th conv (ResNet._forward_h2's hook; lag 0 = after the
+        launched its lag-th conv (ResNet.maps' hook; lag 0 = after the
         stem).  The parts' kernels then run side by side, offset by about one
         layer, so an MFMA-bound conv of one part shares the chip with an
         HBM-bound conv of the other instead of every layer holding the chip by

@@ -311,7 +311,7 @@ def bottleneck_out_h2(y, y_amax, x, x_amax, wb, stride, out_amax=None):
 class TrunkPlan:
     """A networks.ResNet's f16x2 trunk as one native call per forward
     (rr_trunk_h2_*, include/rr.h): uint8 pixels -> x4 (and x3) with their
-    max-|x| records, through the launches ResNet._forward_h2 issues, for the
+    max-|x| records, through the launches ResNet.maps issues, for the
     whole batch on the current stream or, where the batch is large enough
     (rr.h's rule; ``ops.tuning(dev, trunk_parts=1 | 2)`` forces it), in two
     parts on the plan's two streams, part 1 ``lag`` convs behind part 0.  The
@@ -321,46 +321,18 @@ class TrunkPlan:
     def __init__(self, net, lag=1):
         if net.conv_math != "h2":
             raise ValueError("TrunkPlan: the native plan runs the f16x2 trunk (conv_math='h2')")
-        from . import weights as W
         self.net = net
-        self.dev = _dev(net.convs["conv1"][0])
-        cv, h2 = net.convs, net.convs_h2
-        fuse_stem = bool(net.fuse_stem_pool and h2["conv1"].cout == 64)
-        convs = []
-
-        def add(wc, bias, stride, pad, residual, relu, cin=None):
-            convs.append(_lib.TrunkConv(wc.planes.data_ptr() if isinstance(wc, H2Conv) else wc.planes2.data_ptr(),
-                                        wc.iscale.data_ptr(), None if bias is None else bias.data_ptr(),
-                                        wc.cin if cin is None else cin, wc.cout, getattr(wc, "kh", 1),
-                                        getattr(wc, "kw", 1), stride, pad, int(residual), int(relu)))
-
-        add(h2["conv1"], cv["conv1"][1], 2, 3, False, True)
-        fuse_entry = []
-        for li, nb in enumerate(net.layers):
-            for bi in range(nb):
-                p = f"layer{li + 1}.{bi}"
-                stride = 2 if (bi == 0 and li > 0) else 1
-                s1, s2 = W.block_strides(stride, net.stride_on)
-                fused = bi == 0 and net.fuse_downsample and p in net.bneck_h2
-                if bi == 0:
-                    fuse_entry.append(int(fused))
-                    if not fused:
-                        d = f"{p}.downsample.0"
-                        add(h2[d], cv[d][1], stride, 0, False, False)
-                add(h2[f"{p}.conv1"], cv[f"{p}.conv1"][1], s1, 0, False, True)
-                add(h2[f"{p}.conv2"], cv[f"{p}.conv2"][1], s2, 1, False, True)
-                if fused:
-                    wb = net.bneck_h2[p]
-                    add(wb, wb.bias, stride, 0, False, True, cin=wb.planes + wb.cin)
-                else:
-                    add(h2[f"{p}.conv3"], cv[f"{p}.conv3"][1], 1, 0, True, True)
+        convs, fuse_entry = net.plan_convs()
+        self.dev = _dev(convs[0][0])
+        convs = [_lib.TrunkConv(w2.data_ptr(), iscale.data_ptr(), None if bias is None else bias.data_ptr(),
+                                *(int(v) for v in c)) for w2, iscale, bias, *c in convs]
         self._convs = (_lib.TrunkConv * len(convs))(*convs)
         d = _lib.TrunkDesc()
         d.n_stages = len(net.layers)
         for i, nb in enumerate(net.layers):
-            d.blocks[i], d.fuse_entry[i] = nb, fuse_entry[i]
+            d.blocks[i], d.fuse_entry[i] = nb, int(fuse_entry[i])
         d.stride_on = 0 if net.stride_on == "3x3" else 1
-        d.fuse_stem_pool = int(fuse_stem)
+        d.fuse_stem_pool = int(bool(net.fuse_stem_pool and convs[0].cout == 64))
         d.lag = int(lag)
         d.mean[:] = (0.485, 0.456, 0.406)
         d.std[:] = (0.229, 0.224, 0.225)
@@ -420,8 +392,8 @@ class TrunkPlan:
             amax_records(2 if return_x3 else 1, img.device)
         x3 = None
         if return_x3:
-            c3 = self.net.convs_h2[f"layer3.{self.net.layers[2] - 1}.conv3"].cout
-            x3 = torch.empty((b, halved(h, 4), halved(w, 4), c3), dtype=torch.float32, device=img.device)
+            x3 = torch.empty((b, halved(h, 4), halved(w, 4), self.net.outputdim_block4), dtype=torch.float32,
+                             device=img.device)
         if b:
             nbytes = L.rr_trunk_h2_workspace_size(self.plan, b, h, w, self.parts(b, h, w))
             ws = torch.empty(nbytes, dtype=torch.uint8, device=img.device)

@@ -69,21 +69,56 @@ def block_strides(stride, stride_on):
     return (1, stride) if stride_on == "3x3" else (stride, 1)
 
 
+TrunkBlock = collections.namedtuple("TrunkBlock", "prefix stage index entry stride s1 s2 inplanes planes cout stage_end")
+
+
+@functools.lru_cache(maxsize=None)
+def trunk_blocks(arch, stride_on="3x3"):
+    """The bottleneck trunk's block schedule, the one place that decides it: a
+    tuple of TrunkBlock in forward order for arch (a RESNET_LAYERS name).
+    prefix "layer{stage + 1}.{index}"; entry: the block has a downsample
+    projection (a stage's first block); stride: the block's (2 where a stage
+    but the first begins), s1 / s2: conv1's / conv2's (block_strides); the
+    channel chain inplanes -> planes -> planes -> cout; stage_end: a stage's
+    last block."""
+    blocks, inplanes = [], 64
+    for li, nb in enumerate(RESNET_LAYERS[arch]):
+        planes = 64 << li
+        for bi in range(nb):
+            stride = 2 if (bi == 0 and li > 0) else 1
+            blocks.append(TrunkBlock(f"layer{li + 1}.{bi}", li, bi, bi == 0, stride, *block_strides(stride, stride_on),
+                                     inplanes, planes, planes * 4, bi == nb - 1))
+            inplanes = planes * 4
+    return tuple(blocks)
+
+
+def conv_out(n, k, s, p):
+    """Output positions of a conv or pool: n inputs, kernel k, stride s, padding p."""
+    return (n + 2 * p - k) // s + 1
+
+
+def trunk_block_maps(arch, h, w, stride_on="3x3"):
+    """trunk_blocks for an h x w image, each block with its map sizes: yields
+    (block, (H, W) its input, (H1, W1) after the 1x1 conv1, (Ho, Wo) its
+    output); the first input is the stem's 7x7/2 conv and 3x3/2 max-pool of h x w."""
+    H, Wd = (conv_out(conv_out(n, 7, 2, 3), 3, 2, 1) for n in (h, w))
+    for b in trunk_blocks(arch, stride_on):
+        H1, W1 = conv_out(H, 1, b.s1, 0), conv_out(Wd, 1, b.s1, 0)
+        Ho, Wo = conv_out(H1, 3, b.s2, 1), conv_out(W1, 3, b.s2, 1)
+        yield b, (H, Wd), (H1, W1), (Ho, Wo)
+        H, Wd = Ho, Wo
+
+
 def resnet_conv_specs(arch):
     """Ordered (prefix, cout, cin, k) of every conv + its BN prefix, torchvision layout."""
-    layers = RESNET_LAYERS[arch]
     specs = [("conv1", "bn1", 64, 3, 7)]
-    inplanes = 64
-    for li, nblocks in enumerate(layers):
-        planes = 64 * (2 ** li)
-        for bi in range(nblocks):
-            p = f"layer{li + 1}.{bi}"
-            specs.append((f"{p}.conv1", f"{p}.bn1", planes, inplanes, 1))
-            specs.append((f"{p}.conv2", f"{p}.bn2", planes, planes, 3))
-            specs.append((f"{p}.conv3", f"{p}.bn3", planes * 4, planes, 1))
-            if bi == 0:
-                specs.append((f"{p}.downsample.0", f"{p}.downsample.1", planes * 4, inplanes, 1))
-            inplanes = planes * 4
+    for b in trunk_blocks(arch):
+        p = b.prefix
+        specs.append((f"{p}.conv1", f"{p}.bn1", b.planes, b.inplanes, 1))
+        specs.append((f"{p}.conv2", f"{p}.bn2", b.planes, b.planes, 3))
+        specs.append((f"{p}.conv3", f"{p}.bn3", b.cout, b.planes, 1))
+        if b.entry:
+            specs.append((f"{p}.downsample.0", f"{p}.downsample.1", b.cout, b.inplanes, 1))
     return specs
 
 
@@ -1014,8 +1049,7 @@ def senet_block_names(arch):
     """(block prefix, output channels) of every SE bottleneck, in forward order."""
     if arch not in SENET_TRUNKS:
         raise ValueError(f"Unsupported backbone: {arch}")
-    return [(f"layer{li + 1}.{bi}", 256 << li) for li, nb in enumerate(RESNET_LAYERS[SENET_TRUNKS[arch]])
-            for bi in range(nb)]
+    return [(b.prefix, b.cout) for b in trunk_blocks(SENET_TRUNKS[arch])]
 
 
 def senet_check_reduction(reduction):
@@ -1122,29 +1156,15 @@ def synthetic_senet_g2_head(seed, num_classes=8, feature_dim=2048, p=3.0, alpha=
 
 def resnet_conv_flops(arch, h, w, stride_on="3x3"):
     """Algorithmic FLOPs (2*M*N*K) of every trunk conv for one h x w image,
-    following networks.ResNet.forward's strides/pads."""
-    def out(x, k, s, p):
-        return (x + 2 * p - k) // s + 1
-
-    flops = {}
-    H, Wd = out(h, 7, 2, 3), out(w, 7, 2, 3)
-    flops["conv1"] = 2 * H * Wd * 64 * 7 * 7 * 3
-    H, Wd = out(H, 3, 2, 1), out(Wd, 3, 2, 1)
-    inplanes = 64
-    for li, nb in enumerate(RESNET_LAYERS[arch]):
-        planes = 64 * 2 ** li
-        for bi in range(nb):
-            s = 2 if (bi == 0 and li > 0) else 1
-            s1, s2 = block_strides(s, stride_on)
-            p = f"layer{li + 1}.{bi}"
-            H1, W1 = out(H, 1, s1, 0), out(Wd, 1, s1, 0)
-            Ho, Wo = out(H1, 3, s2, 1), out(W1, 3, s2, 1)
-            if bi == 0:
-                flops[p + ".downsample.0"] = 2 * Ho * Wo * planes * 4 * inplanes
-            flops[p + ".conv1"] = 2 * H1 * W1 * planes * inplanes
-            flops[p + ".conv2"] = 2 * Ho * Wo * planes * planes * 9
-            flops[p + ".conv3"] = 2 * Ho * Wo * planes * 4 * planes
-            H, Wd, inplanes = Ho, Wo, planes * 4
+    following the trunk's strides/pads (trunk_block_maps)."""
+    flops = {"conv1": 2 * conv_out(h, 7, 2, 3) * conv_out(w, 7, 2, 3) * 64 * 7 * 7 * 3}
+    for b, _, (H1, W1), (Ho, Wo) in trunk_block_maps(arch, h, w, stride_on):
+        p = b.prefix
+        if b.entry:
+            flops[p + ".downsample.0"] = 2 * Ho * Wo * b.cout * b.inplanes
+        flops[p + ".conv1"] = 2 * H1 * W1 * b.planes * b.inplanes
+        flops[p + ".conv2"] = 2 * Ho * Wo * b.planes * b.planes * 9
+        flops[p + ".conv3"] = 2 * Ho * Wo * b.cout * b.planes
     return flops
 
 
@@ -1155,40 +1175,27 @@ def resnet_conv_bytes(arch, h, w, batch, stride_on="3x3", weight_bytes=6, fused=
     once, the block's fp32 identity read once by the residual conv3, and the
     weights once per launch (`weight_bytes` per parameter: 6 = the split-bf16
     core's three bf16 planes, 4 = fp32 or the f16x2 core's two fp16 planes).
-    fused (the f16x2 trunk, networks.ResNet._forward_h2): the stem writes only
+    fused (the f16x2 trunk, networks.ResNet): the stem writes only
     its max-pooled map (rr_stem_pool_h2), and a stage's first block computes
     conv3 and the downsample projection as one GEMM (rr_bottleneck_out_h2),
     which reads the block input at the sampled pixels and writes no projected
     identity (its bytes are split between the two names)."""
-    def out(x, k, s, p):
-        return (x + 2 * p - k) // s + 1
-
-    by = {}
-    H, Wd = out(h, 7, 2, 3), out(w, 7, 2, 3)
-    Hp, Wp = out(H, 3, 2, 1), out(Wd, 3, 2, 1)
-    by["conv1"] = batch * (h * w * 4 + (Hp * Wp if fused else H * Wd) * 64) * 4 + 64 * 7 * 7 * 4 * weight_bytes
-    H, Wd = Hp, Wp
-    inplanes = 64
-    for li, nb in enumerate(RESNET_LAYERS[arch]):
-        planes = 64 * 2 ** li
-        for bi in range(nb):
-            s = 2 if (bi == 0 and li > 0) else 1
-            s1, s2 = block_strides(s, stride_on)
-            p = f"layer{li + 1}.{bi}"
-            H1, W1 = out(H, 1, s1, 0), out(Wd, 1, s1, 0)
-            Ho, Wo = out(H1, 3, s2, 1), out(W1, 3, s2, 1)
-            x_in = H * Wd * inplanes
-            wd_by = planes * 4 * inplanes * weight_bytes
-            if bi == 0 and fused:
-                by[p + ".downsample.0"] = batch * Ho * Wo * inplanes * 4 + wd_by
-            elif bi == 0:
-                by[p + ".downsample.0"] = batch * (x_in + Ho * Wo * planes * 4) * 4 + wd_by
-            by[p + ".conv1"] = batch * (x_in + H1 * W1 * planes) * 4 + planes * inplanes * weight_bytes
-            by[p + ".conv2"] = batch * (H1 * W1 * planes + Ho * Wo * planes) * 4 + planes * planes * 9 * weight_bytes
-            n_res = 0 if (bi == 0 and fused) else 1  # the identity map read by the residual epilogue
-            by[p + ".conv3"] = batch * (Ho * Wo * planes + (1 + n_res) * Ho * Wo * planes * 4) * 4 + \
-                planes * 4 * planes * weight_bytes
-            H, Wd, inplanes = Ho, Wo, planes * 4
+    H, Wd = conv_out(h, 7, 2, 3), conv_out(w, 7, 2, 3)
+    if fused:
+        H, Wd = conv_out(H, 3, 2, 1), conv_out(Wd, 3, 2, 1)
+    by = {"conv1": batch * (h * w * 4 + H * Wd * 64) * 4 + 64 * 7 * 7 * 4 * weight_bytes}
+    for b, (H, Wd), (H1, W1), (Ho, Wo) in trunk_block_maps(arch, h, w, stride_on):
+        p, planes, inplanes = b.prefix, b.planes, b.inplanes
+        x_in = H * Wd * inplanes
+        wd_by = b.cout * inplanes * weight_bytes
+        if b.entry and fused:
+            by[p + ".downsample.0"] = batch * Ho * Wo * inplanes * 4 + wd_by
+        elif b.entry:
+            by[p + ".downsample.0"] = batch * (x_in + Ho * Wo * b.cout) * 4 + wd_by
+        by[p + ".conv1"] = batch * (x_in + H1 * W1 * planes) * 4 + planes * inplanes * weight_bytes
+        by[p + ".conv2"] = batch * (H1 * W1 * planes + Ho * Wo * planes) * 4 + planes * planes * 9 * weight_bytes
+        n_res = 0 if (b.entry and fused) else 1  # the identity map read by the residual epilogue
+        by[p + ".conv3"] = batch * (Ho * Wo * planes + (1 + n_res) * Ho * Wo * b.cout) * 4 + b.cout * planes * weight_bytes
     return by
 
 

@@ -1,8 +1,10 @@
 """The native trunk plan (rr_trunk_h2_*, ops.TrunkPlan): one part is the
 launch-by-launch trunk bit for bit, two parts are the one-part plan on each
-slice, the join orders the caller's stream behind both parts, the library's
+slice (both also with the stage entries and the stem's pool unfused: the
+plan's separate downsample conv and its max-pool op), the join orders the caller's stream behind both parts, the library's
 pick stays at one part for small batches, and the class timer returns the
 union of the launch intervals."""
+import contextlib
 import ctypes
 
 import numpy as np
@@ -37,10 +39,24 @@ def _same(a, b):
     return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
 
 
-@pytest.mark.parametrize("hw", SIZES)
-@pytest.mark.parametrize("stride_on", ["3x3", "1x1"])
-def test_one_part_is_the_reference_trunk(nets, stride_on, hw):
-    net = nets[stride_on]
+# (fuse_downsample, fuse_stem_pool): the plan's ENTRY / STEM_POOL ops, and its
+# separate downsample conv into the identity buffer / its MAXPOOL op
+FUSIONS = [(True, True), (False, True), (True, False), (False, False)]
+
+
+@contextlib.contextmanager
+def _fusions(net, fuse_downsample, fuse_stem_pool):
+    """net with both flags set for the block (the eager trunk reads them per
+    call, net.plan() keeps one plan per combination)."""
+    saved = net.fuse_downsample, net.fuse_stem_pool
+    net.fuse_downsample, net.fuse_stem_pool = fuse_downsample, fuse_stem_pool
+    try:
+        yield net
+    finally:
+        net.fuse_downsample, net.fuse_stem_pool = saved
+
+
+def _one_part_is_the_reference_trunk(net, hw):
     img = _imgs(3, *hw, seed=1)
     ref = net.forward(ops.preprocess_u8(img, out_c=4), return_x3=True, return_x3_amax=True, return_amax=True)
     with ops.tuning(0, trunk_parts=1):
@@ -54,10 +70,19 @@ def test_one_part_is_the_reference_trunk(nets, stride_on, hw):
     assert _same(ref[1], x4) and torch.equal(ref[3], x4a)
 
 
-@pytest.mark.parametrize("lag", [1, 0, 3])
 @pytest.mark.parametrize("hw", SIZES)
-def test_two_parts_are_the_plan_on_each_slice(nets, hw, lag):
-    net = nets["3x3"]
+@pytest.mark.parametrize("stride_on", ["3x3", "1x1"])
+def test_one_part_is_the_reference_trunk(nets, stride_on, hw):
+    _one_part_is_the_reference_trunk(nets[stride_on], hw)
+
+
+@pytest.mark.parametrize("fuse_downsample,fuse_stem_pool", FUSIONS)
+def test_one_part_is_the_reference_trunk_under_each_fusion(nets, fuse_downsample, fuse_stem_pool):
+    with _fusions(nets["3x3"], fuse_downsample, fuse_stem_pool) as net:
+        _one_part_is_the_reference_trunk(net, SIZES[0])
+
+
+def _two_parts_are_the_plan_on_each_slice(net, hw, lag):
     plan = net.plan(lag)
     img = _imgs(5, *hw, seed=2)
     with ops.tuning(0, trunk_parts=1):
@@ -75,6 +100,18 @@ def test_two_parts_are_the_plan_on_each_slice(nets, hw, lag):
     assert torch.equal(x4a, torch.maximum(a[3], b[3]))
     # x3's record is folded from the parts' own records: the same maximum
     assert ops.amax_value(x3a) == max(ops.amax_value(a[2]), ops.amax_value(b[2]))
+
+
+@pytest.mark.parametrize("lag", [1, 0, 3])
+@pytest.mark.parametrize("hw", SIZES)
+def test_two_parts_are_the_plan_on_each_slice(nets, hw, lag):
+    _two_parts_are_the_plan_on_each_slice(nets["3x3"], hw, lag)
+
+
+@pytest.mark.parametrize("fuse_downsample,fuse_stem_pool", FUSIONS)
+def test_two_parts_are_the_plan_on_each_slice_under_each_fusion(nets, fuse_downsample, fuse_stem_pool):
+    with _fusions(nets["3x3"], fuse_downsample, fuse_stem_pool) as net:
+        _two_parts_are_the_plan_on_each_slice(net, SIZES[0], 1)
 
 
 @pytest.mark.parametrize("side_stream", [False, True])

@@ -11,34 +11,22 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from research_image_retrieval_amd import ops  # noqa: E402
-from research_image_retrieval_amd import weights as W  # noqa: E402
 from research_image_retrieval_amd.networks import ResNet  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 1280
 CH = [int(c) for c in (sys.argv[2] if len(sys.argv) > 2 else "1280,640,320,160,80,40").split(",")]
 dev = torch.device("cuda:0")
 net = ResNet("resnet101", seed=0, device=dev)
-cv, h2 = net.convs, net.convs_h2
 
 
 def stage(li, x, xa_rec):
-    """layer{li+1} on x (record xa_rec), the same launches as _forward_h2."""
-    nb = net.layers[li]
-    rec = ops.amax_records(3 * nb, x.device)
-    xa, r = xa_rec, 0
-    for bi in range(nb):
-        p = f"layer{li + 1}.{bi}"
-        s1, s2 = W.block_strides(2 if (bi == 0 and li > 0) else 1, net.stride_on)
-        fused = bi == 0 and p in net.bneck_h2
-        d = f"{p}.downsample.0"
-        idn = ops.conv2d_h2(x, xa, h2[d], cv[d][1], s1 * s2, 0, None, False) if bi == 0 and not fused else x
-        y = ops.conv2d_h2(x, xa, h2[f"{p}.conv1"], cv[f"{p}.conv1"][1], s1, 0, None, True, rec[r])
-        y = ops.conv2d_h2(y, rec[r], h2[f"{p}.conv2"], cv[f"{p}.conv2"][1], s2, 1, None, True, rec[r + 1])
-        if fused:
-            x = ops.bottleneck_out_h2(y, rec[r + 1], x, xa, net.bneck_h2[p], s1 * s2, rec[r + 2])
-        else:
-            x = ops.conv2d_h2(y, rec[r + 1], h2[f"{p}.conv3"], cv[f"{p}.conv3"][1], 1, 0, idn, True, rec[r + 2])
-        xa, r = rec[r + 2], r + 3
+    """layer{li+1} on x (record xa_rec): the launches ResNet.maps issues for that stage."""
+    blocks = [b for b in net.blocks if b.stage == li]
+    rec = ops.amax_records(3 * len(blocks), x.device)
+    xa = xa_rec
+    for k, b in enumerate(blocks):
+        x = net._block(x, xa, b, rec[3 * k:3 * k + 3], lambda i: None, 0)
+        xa = rec[3 * k + 2]
     return x, xa
 
 

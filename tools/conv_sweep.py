@@ -14,23 +14,14 @@ from research_image_retrieval_amd import weights as W  # noqa: E402
 
 
 def conv_launches(arch, b, h=224, w=224):
-    out = lambda x, k, s, p: (x + 2 * p - k) // s + 1  # noqa: E731
     L = collections.Counter()
-    H, Wd = h, w
-    L[(b, H, Wd, 4, 64, 7, 2, 3, False, True)] += 1  # stem on NHWC4
-    H, Wd = out(out(H, 7, 2, 3), 3, 2, 1), out(out(Wd, 7, 2, 3), 3, 2, 1)
-    inpl = 64
-    for li, nb in enumerate(W.RESNET_LAYERS[arch]):
-        pl = 64 * 2 ** li
-        for bi in range(nb):
-            s = 2 if (bi == 0 and li > 0) else 1
-            Ho, Wo = out(H, 3, s, 1), out(Wd, 3, s, 1)
-            if bi == 0:
-                L[(b, H, Wd, inpl, pl * 4, 1, s, 0, False, False)] += 1
-            L[(b, H, Wd, inpl, pl, 1, 1, 0, False, True)] += 1
-            L[(b, H, Wd, pl, pl, 3, s, 1, False, True)] += 1
-            L[(b, Ho, Wo, pl, pl * 4, 1, 1, 0, True, True)] += 1
-            H, Wd, inpl = Ho, Wo, pl * 4
+    L[(b, h, w, 4, 64, 7, 2, 3, False, True)] += 1  # stem on NHWC4
+    for k, (H, Wd), _, (Ho, Wo) in W.trunk_block_maps(arch, h, w):
+        if k.entry:
+            L[(b, H, Wd, k.inplanes, k.cout, 1, k.stride, 0, False, False)] += 1
+        L[(b, H, Wd, k.inplanes, k.planes, 1, 1, 0, False, True)] += 1
+        L[(b, H, Wd, k.planes, k.planes, 3, k.stride, 1, False, True)] += 1
+        L[(b, Ho, Wo, k.planes, k.cout, 1, 1, 0, True, True)] += 1
     return L
 
 

@@ -37,64 +37,66 @@ def rep(name, got, ref):
     print(f"{name:28s} {tuple(ref.shape)} err {e:.2e} max {ref.abs().max().item():.3f}{flag}", flush=True)
 
 
+def conv(x, name, stride, pad, relu, residual=None):
+    """One folded conv of the trunk on the exact-fp32 core."""
+    w, b = net.convs[name]
+    return ops.conv2d(x, w, b, stride, pad, residual, relu)
+
+
 if os.environ.get("DIAG_CHAIN"):
     # chained: GPU chain vs oracle chain per block, and each GPU conv's error on
     # the GPU chain's own input (oracle conv run on that same input)
     with torch.no_grad():
         g = ops.preprocess_u8(imgs.to(dev), out_c=4)
         r = x
-        g = net._conv(g, "conv1", 2, 3, True)
+        g = conv(g, "conv1", 2, 3, True)
         rep("conv1 (own input)", nchw(g), F.relu(bn(F.conv2d(nchw(ops.preprocess_u8(imgs.to(dev), out_c=4))[:, :3],
                                                                 sd["conv1.weight"], None, 2, 3), sd, "bn1")))
         g = ops.maxpool2d(g, 3, 2, 1)
         r = F.max_pool2d(F.relu(bn(F.conv2d(r, sd["conv1.weight"], None, 2, 3), sd, "bn1")), 3, 2, 1)
         rep("chain stem", nchw(g), r)
-        for li, nb in enumerate(W.RESNET_LAYERS[arch]):
-            for bi in range(nb):
-                p = f"layer{li + 1}.{bi}"
-                s1, s2 = W.block_strides(2 if (bi == 0 and li > 0) else 1, so)
-                gi = nchw(g)
-                gid = net._conv(g, p + ".downsample.0", s1 * s2, 0, False) if bi == 0 else g
-                g1 = net._conv(g, p + ".conv1", s1, 0, True)
-                g2 = net._conv(g1, p + ".conv2", s2, 1, True)
-                g3 = net._conv(g2, p + ".conv3", 1, 0, True, residual=gid)
-                o1 = F.relu(bn(F.conv2d(gi, sd[p + ".conv1.weight"], None, s1), sd, p + ".bn1"))
-                rep(p + ".conv1 (own in)", nchw(g1), o1)
-                o2 = F.relu(bn(F.conv2d(nchw(g1), sd[p + ".conv2.weight"], None, s2, 1), sd, p + ".bn2"))
-                rep(p + ".conv2 (own in)", nchw(g2), o2)
-                oid = bn(F.conv2d(gi, sd[p + ".downsample.0.weight"], None, s1 * s2), sd,
-                         p + ".downsample.1") if bi == 0 else gi
-                o3 = F.relu(oid + bn(F.conv2d(nchw(g2), sd[p + ".conv3.weight"]), sd, p + ".bn3"))
-                rep(p + ".conv3 (own in)", nchw(g3), o3)
-                idn = r
-                if bi == 0:
-                    idn = bn(F.conv2d(r, sd[p + ".downsample.0.weight"], None, s1 * s2), sd, p + ".downsample.1")
-                y = F.relu(bn(F.conv2d(r, sd[p + ".conv1.weight"], None, s1), sd, p + ".bn1"))
-                y = F.relu(bn(F.conv2d(y, sd[p + ".conv2.weight"], None, s2, 1), sd, p + ".bn2"))
-                r = F.relu(idn + bn(F.conv2d(y, sd[p + ".conv3.weight"]), sd, p + ".bn3"))
-                g = g3
-                rep("chain " + p, nchw(g), r)
+        for k in net.blocks:
+            p, s1, s2 = k.prefix, k.s1, k.s2
+            gi = nchw(g)
+            gid = conv(g, p + ".downsample.0", k.stride, 0, False) if k.entry else g
+            g1 = conv(g, p + ".conv1", s1, 0, True)
+            g2 = conv(g1, p + ".conv2", s2, 1, True)
+            g3 = conv(g2, p + ".conv3", 1, 0, True, residual=gid)
+            o1 = F.relu(bn(F.conv2d(gi, sd[p + ".conv1.weight"], None, s1), sd, p + ".bn1"))
+            rep(p + ".conv1 (own in)", nchw(g1), o1)
+            o2 = F.relu(bn(F.conv2d(nchw(g1), sd[p + ".conv2.weight"], None, s2, 1), sd, p + ".bn2"))
+            rep(p + ".conv2 (own in)", nchw(g2), o2)
+            oid = bn(F.conv2d(gi, sd[p + ".downsample.0.weight"], None, k.stride), sd,
+                     p + ".downsample.1") if k.entry else gi
+            o3 = F.relu(oid + bn(F.conv2d(nchw(g2), sd[p + ".conv3.weight"]), sd, p + ".bn3"))
+            rep(p + ".conv3 (own in)", nchw(g3), o3)
+            idn = r
+            if k.entry:
+                idn = bn(F.conv2d(r, sd[p + ".downsample.0.weight"], None, k.stride), sd, p + ".downsample.1")
+            y = F.relu(bn(F.conv2d(r, sd[p + ".conv1.weight"], None, s1), sd, p + ".bn1"))
+            y = F.relu(bn(F.conv2d(y, sd[p + ".conv2.weight"], None, s2, 1), sd, p + ".bn2"))
+            r = F.relu(idn + bn(F.conv2d(y, sd[p + ".conv3.weight"]), sd, p + ".bn3"))
+            g = g3
+            rep("chain " + p, nchw(g), r)
     sys.exit(0)
 
 with torch.no_grad():
     xu = ops.preprocess_u8(imgs.to(dev), out_c=4)
     rep("preprocess", nchw(xu)[:, :3], x)
     y = F.relu(bn(F.conv2d(x, sd["conv1.weight"], None, 2, 3), sd, "bn1"))
-    rep("conv1", nchw(net._conv(nhwc(F.pad(x, (0, 0, 0, 0, 0, 1))), "conv1", 2, 3, True)), y)
+    rep("conv1", nchw(conv(nhwc(F.pad(x, (0, 0, 0, 0, 0, 1))), "conv1", 2, 3, True)), y)
     xin = F.max_pool2d(y, 3, 2, 1)
     rep("maxpool", nchw(ops.maxpool2d(nhwc(y), 3, 2, 1)), xin)
-    for li, nb in enumerate(W.RESNET_LAYERS[arch]):
-        for bi in range(nb):
-            p = f"layer{li + 1}.{bi}"
-            s1, s2 = W.block_strides(2 if (bi == 0 and li > 0) else 1, so)
-            idn = xin
-            if bi == 0:
-                idn = bn(F.conv2d(xin, sd[p + ".downsample.0.weight"], None, s1 * s2), sd, p + ".downsample.1")
-                rep(p + ".downsample", nchw(net._conv(nhwc(xin), p + ".downsample.0", s1 * s2, 0, False)), idn)
-            y1 = F.relu(bn(F.conv2d(xin, sd[p + ".conv1.weight"], None, s1), sd, p + ".bn1"))
-            rep(p + ".conv1", nchw(net._conv(nhwc(xin), p + ".conv1", s1, 0, True)), y1)
-            y2 = F.relu(bn(F.conv2d(y1, sd[p + ".conv2.weight"], None, s2, 1), sd, p + ".bn2"))
-            rep(p + ".conv2", nchw(net._conv(nhwc(y1), p + ".conv2", s2, 1, True)), y2)
-            y3 = F.relu(idn + bn(F.conv2d(y2, sd[p + ".conv3.weight"]), sd, p + ".bn3"))
-            rep(p + ".conv3+res", nchw(net._conv(nhwc(y2), p + ".conv3", 1, 0, True, residual=nhwc(idn))), y3)
-            xin = y3
+    for k in net.blocks:
+        p, s1, s2 = k.prefix, k.s1, k.s2
+        idn = xin
+        if k.entry:
+            idn = bn(F.conv2d(xin, sd[p + ".downsample.0.weight"], None, k.stride), sd, p + ".downsample.1")
+            rep(p + ".downsample", nchw(conv(nhwc(xin), p + ".downsample.0", k.stride, 0, False)), idn)
+        y1 = F.relu(bn(F.conv2d(xin, sd[p + ".conv1.weight"], None, s1), sd, p + ".bn1"))
+        rep(p + ".conv1", nchw(conv(nhwc(xin), p + ".conv1", s1, 0, True)), y1)
+        y2 = F.relu(bn(F.conv2d(y1, sd[p + ".conv2.weight"], None, s2, 1), sd, p + ".bn2"))
+        rep(p + ".conv2", nchw(conv(nhwc(y1), p + ".conv2", s2, 1, True)), y2)
+        y3 = F.relu(idn + bn(F.conv2d(y2, sd[p + ".conv3.weight"]), sd, p + ".bn3"))
+        rep(p + ".conv3+res", nchw(conv(nhwc(y2), p + ".conv3", 1, 0, True, residual=nhwc(idn))), y3)
+        xin = y3
